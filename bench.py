@@ -59,6 +59,15 @@ def main():
                     help="--via-dataframe: shard residency in HBM or the pinned-ring stream (ShardLoader)")
     ap.add_argument("--seq", type=int, default=512)
     ap.add_argument("--layers", type=int, default=12)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write DIR/loss.npy (the loss the last timed step returned) and "
+                         "DIR/weight_norms.npy (the L2 norm of every fp32 parameter not initialised to zero, after "
+                         "that step's update), float32; the run rewinds to its seeded initial weights before its "
+                         "last timed step so that the arrays repeat from run to run (see rewind_state; figures "
+                         "in docs/PERFORMANCE.md)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that are not part of the headline figure (they take runs of "
+                         "their own): the stand-alone full-gradient all-reduce time of an N > 1 job (config.comm_ms)")
     args = ap.parse_args()
     if args.model == "vgg16" and args.image == 224:
         args.image = 32
@@ -105,6 +114,7 @@ def main():
         x, y = stream.next()
         return step_fn(x, y)
 
+    w0 = model.arena.master.clone() if args.dump_outputs else None
     for _ in range(args.warmup):
         step()
     pg.barrier()
@@ -112,18 +122,22 @@ def main():
     ddp.exposed_comm_ms(reset=True)  # exposed-comm statistics cover the timed steps only
     t0 = time.perf_counter()
     loss = None
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if w0 is not None and i == max(args.steps - _REWIND, 0):
+            rewind_state(model, w0)
         loss = step()
     torch.cuda.synchronize(dev) if dev.type == "cuda" else None
     pg.barrier()
     dt = time.perf_counter() - t0
     dt_max = pg.max_scalar(dt)
-    comm = comm_stats(ddp, pg)
+    comm = comm_stats(ddp, pg, args.full)
     ms = dt_max * 1000.0 / args.steps
     gb = args.batch * world
     ips = gb * args.steps / dt_max
     lossv = float(loss) if loss is not None else float("nan")
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, loss=lossv, weight_norms=weight_norms(model, w0))
         out = {
             "metric": ("images/sec (whole node) ResNet-50 ImageNet-shape at 1/2/4/8 MI355X" if args.model == "resnet50"
                        else "images/sec (whole node) VGG-16 CIFAR-shape"),
@@ -171,16 +185,68 @@ def make_step(ddp, args):
     return CompiledTrainStep(m, warmup=2)
 
 
-def comm_stats(ddp, pg):
+_DUMP_CAP = 8 << 20  # elements per dumped array (32 MB of float32; --dump-outputs stays far below 64 MB in all)
+
+
+def dump_outputs(directory, **arrays):
+    """--dump-outputs: write each array as ``directory/<name>.npy`` in float32.  An array of more than
+    ``_DUMP_CAP`` elements is reduced to that many of its elements, at sorted positions drawn once from a fixed
+    seed (the same positions for the same size in every run and build)."""
+    if not directory:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy()
+        a = np.atleast_1d(np.asarray(a, dtype=np.float32))
+        if a.size > _DUMP_CAP:
+            idx = np.sort(np.random.default_rng(20240229).choice(a.size, _DUMP_CAP, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
+_REWIND = 1  # timed steps run after the rewind
+
+
+def rewind_state(model, w0):
+    """--dump-outputs: put the model back to its initial weights ``w0`` and an empty optimizer state, in stream
+    order and without a host synchronisation (three device copies / fills, about 0.1 ms for ResNet-50, once per
+    run).  The steps themselves are the default ones (same kernels, same captured graph).  Why: the default kernels
+    add partial sums with fp32 atomics in no fixed order, and training amplifies that rounding from step to step,
+    so after a few dozen steps two runs of one build are far apart.  From the same state the last step's loss
+    (its forward pass) and the weight norms after it (its backward pass and update) agree to rounding; already one
+    update at lr 0.1 between the rewind and the loss multiplies the rounding by a factor that depends on the shape."""
+    a = model.arena
+    with torch.no_grad():
+        a.master.copy_(w0)
+        a.sync_compute()
+        for v in model.optimizer.state.values():
+            v.zero_()
+
+
+def weight_norms(model, w0):
+    """L2 norm of the fp32 weights of every parameter, in arena order, that does not start at zero (``w0``: the
+    initial arena).  A zero-initialised bias or BatchNorm shift holds nothing but the last update, so its
+    norm is the norm of a gradient whose rounding noise is a tenth of it; beside its starting weights that
+    noise is small."""
+    with torch.no_grad():
+        keep = [p for p in model.arena.params if bool(w0[p.offset:p.offset + p.snumel].any())]
+        return torch.stack([p.master.detach().float().norm() for p in keep])
+
+
+def comm_stats(ddp, pg, full=False):
     """Communication evidence for the JSON line: exposed (un-overlapped) all-reduce time per
-    timed step, and the stand-alone full-gradient all-reduce time (max over ranks)."""
+    timed step and, with ``--full``, the stand-alone full-gradient all-reduce time (max over ranks)."""
     if not pg.distributed:
         return {"comm_ms": None, "exposed_comm_ms": None, "bucket_mb": ddp.bucket_mb, "buckets": len(ddp.buckets)}
     exposed = ddp.exposed_comm_ms()
-    full = ddp.measure_allreduce(iters=5)
     exposed = pg.max_scalar(exposed if exposed is not None else 0.0)
-    full = pg.max_scalar(full if full is not None else 0.0)
-    return {"comm_ms": round(full, 3), "exposed_comm_ms": round(exposed, 3), "bucket_mb": ddp.bucket_mb,
+    if full:  # a measurement of its own (warm-up + 5 all-reduces of the whole gradient arena)
+        full = ddp.measure_allreduce(iters=5)
+        full = round(pg.max_scalar(full if full is not None else 0.0), 3)
+    else:
+        full = None
+    return {"comm_ms": full, "exposed_comm_ms": round(exposed, 3), "bucket_mb": ddp.bucket_mb,
             "buckets": len(ddp.buckets), "reduce_dtype": "bf16" if ddp.bf16_algo is not None else "fp32",
             "bf16_algo": ddp.bf16_algo, "optimizer_overlap": ddp.overlap_optimizer and ddp.model.optimizer.ranged_ok,
             "grad_mb": round(ddp.grad_bytes / 2**20, 1), "backend": pg.backend, "forced_pg": pg.forced,
@@ -214,6 +280,7 @@ def bench_nyiso(args):
         out = ddl_nyiso.main(argv)
     r = out["results"][cell]
     ref = _NYISO_REF[cell]
+    dump_outputs(args.dump_outputs, mape=r["mape"])  # the workflow hands back the trained model's test error
     print(json.dumps({
         "metric": f"training time (s) NYISO {cell}(128)+Dense(1) ADAG {args.workers} workers {args.epochs} epochs",
         "value": round(r["time_s"], 4), "unit": "s", "n_gpus": gpus, "steps": int(r["updates"]), "warmup": 0,
@@ -264,6 +331,7 @@ def bench_via_dataframe(args, pg):
     steps = res[0]["timed_steps"]
     gb = args.batch * world
     if rank == 0:
+        dump_outputs(args.dump_outputs, loss=float(res[0]["history"][-1]))  # the trainer's own loop: no rewind
         print(json.dumps({
             "metric": "images/sec (whole node) ResNet-50 ImageNet-shape at 1/2/4/8 MI355X",
             "value": round(gb * steps / dt_max, 2), "unit": "images/sec", "n_gpus": world, "steps": steps,
@@ -303,6 +371,7 @@ def bench_bert(args, pg):
         it[0] += 1
         return step_fn(x, y)
 
+    w0 = model.arena.master.clone() if args.dump_outputs else None
     for _ in range(args.warmup):
         step()
     pg.barrier()
@@ -310,15 +379,19 @@ def bench_bert(args, pg):
     ddp.exposed_comm_ms(reset=True)  # exposed-comm statistics cover the timed steps only
     t0 = time.perf_counter()
     loss = None
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if w0 is not None and i == max(args.steps - _REWIND, 0):
+            rewind_state(model, w0)
         loss = step()
     torch.cuda.synchronize(dev) if dev.type == "cuda" else None
     pg.barrier()
     dt_max = pg.max_scalar(time.perf_counter() - t0)
-    comm = comm_stats(ddp, pg)
+    comm = comm_stats(ddp, pg, args.full)
     gb = args.batch * world
     tps = gb * args.seq * args.steps / dt_max
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, loss=float(loss), weight_norms=weight_norms(model, w0))
         print(json.dumps({
             "metric": "tokens/sec (whole node) BERT-base MLM seq-len 512",
             "value": round(tps, 1), "unit": "tokens/sec", "n_gpus": world, "steps": args.steps,

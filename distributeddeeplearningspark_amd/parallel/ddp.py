@@ -44,7 +44,7 @@ collectives over xGMI:
 * Timing (``timing=True``): HIP events on the compute stream bracket the part of the
   step that waits for communication (end of backward -> all buckets reduced), giving the
   *exposed* communication time; :meth:`measure_allreduce` times the full-gradient
-  all-reduce on its own (``comm_ms`` in ``bench.py``'s JSON).
+  all-reduce on its own (``comm_ms`` in the JSON of ``bench.py --full``).
 """
 from __future__ import annotations
 
