@@ -248,12 +248,43 @@ int rnn_fwd(int cell, const float* xw, const float* x, const float* W, const flo
             float* hs, float* cs, float* gates, float* y, int B, int T, int H, int rs, int act, int ract,
             hipStream_t s);
 // gU/gW/gb (fp32, nullable gb) += parameter gradients from dgates (one launch, atomics)
+// rev: the saved tensors are those of a reverse-direction recurrence (h_{t-1} lives in slot t + 1, see RnnDir)
 int rnn_param_grad(int cell, const float* dg, const float* hs, const float* gates, const float* x, float* gU,
-                   float* gW, float* gb, int B, int T, int H, int I, hipStream_t s);
+                   float* gW, float* gb, int B, int T, int H, int I, hipStream_t s, int rev = 0);
 // UT = U^T [G*H][H] (generic path only); dgates [B][T][G*H] = gradients of the gate pre-activations
 bool rnn_bwd_uses_ut(int H);
 int rnn_bwd(int cell, const float* dy, const float* U, const float* UT, const float* hs, const float* cs,
             const float* gates, float* dgates, int B, int T, int H, int rs, int act, int ract, hipStream_t s);
+
+// Directed recurrences (go_backwards / Bidirectional): ONE launch runs ndir (1 or 2) recurrences over the same
+// batch, blockIdx.y = direction.  Processing step s = 0..T-1 of direction d touches memory time index
+// tm = rev[d] ? T-1-s : s.  x, xw, gates, dgates, hs and cs stay in MEMORY time order: a forward direction keeps
+// the state after step tm in slot tm + 1 (slot 0 = zero state), a reverse direction in slot tm (slot T = zero
+// state), so "previous state" is slot tm + rev and every contraction against x is direction-blind.
+// y / dy rows are ldy floats wide and a direction owns columns [yoff, yoff + H): a Bidirectional concat output
+// is written (and its gradient read) in place.  yproc[d]: sequence rows of y / dy in processing order (a bare
+// go_backwards layer), else in input time order (Bidirectional).  dy is scaled by dscale on load (ave: 0.5).
+struct RnnDir {
+  const float* xw[2];  // [B T][GH] projection (+ bias), or null: fused in-kernel from x / W / b (reg path, I <= 8)
+  const float* W[2];
+  const float* b[2];
+  const float* U[2];   // [H][GH]
+  const float* UT[2];  // [GH][H], generic backward only
+  float* hs[2];        // [B][T+1][H]
+  float* cs[2];        // [B][T+1][H] (LSTM)
+  float* gates[2];     // [B][T][GH]
+  float* dgates[2];    // [B][T][GH] (backward)
+  float* y[2];         // forward output base
+  const float* dy[2];  // backward input base
+  int rev[2], yoff[2], yproc[2];
+  int ldy;
+  float dscale;
+};
+int rnn_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
+                int ract, hipStream_t s);
+int rnn_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract, hipStream_t s);
+// out = scale * (a + b), fp32 (Bidirectional sum / ave merge)
+int bidir_merge(const float* a, const float* b, float* out, long n, float scale, hipStream_t s);
 
 // ---------------- Keras layer element-wise ops (kernels/layer_ops.hip) ----------------
 // activation codes shared by the standalone Activation layer and the recurrent cells

@@ -11,6 +11,14 @@
 // Backward (BPTT) runs the same persistent structure in reverse time, propagating dh (and dc)
 // with U^T columns per thread; it emits the pre-activation gate gradients of every step so
 // that dW, dU, db and dx are plain GEMMs / reductions afterwards.
+//
+// Directed instantiations (DIR = true; go_backwards / Bidirectional, RnnDir in ddl_ops.h): the workgroup takes its
+// direction from blockIdx.y, picks that direction's pointers out of the table and maps processing step s to memory
+// time index t = rev ? T-1-s : s.  Saved tensors stay in memory time order; a reverse direction keeps the state
+// after step t in slot t (slot T = zero state), so the previous state is slot t + rev and the next one t + 1 - rev.
+// With DIR = false every direction value below is a compile-time constant and the code is the forward-only one.
+#include <type_traits>
+
 #include "ddl_act.h"
 
 namespace ddl {
@@ -18,18 +26,73 @@ namespace {
 
 constexpr int BB = 4;  // batch rows per workgroup
 
+struct NoDir {};
+template <bool DIR>
+using DirArg = std::conditional_t<DIR, RnnDir, NoDir>;      // trailing argument of the generic kernels
+template <bool DIR>
+using RegArg = std::conditional_t<DIR, RnnDir, RnnRep>;     // ... of the register-resident kernels
+
+// Direction state of a workgroup and the index expressions that depend on it.  row = batch row, s = processing
+// step, t = time(s) its memory time index.  With DIR = false they are literally the forward-only expressions.
+template <bool DIR>
+struct DirOf {
+  int rev = 0, yoff = 0, ldy = 0, yproc = 0;
+  float dscale = 1.f;
+  __device__ __forceinline__ void load(const DirArg<DIR>& a, int d) {
+    if constexpr (DIR) {
+      rev = a.rev[d]; yoff = a.yoff[d]; ldy = a.ldy; yproc = a.yproc[d]; dscale = a.dscale;
+    }
+  }
+  __device__ __forceinline__ int time(int s, int T) const {
+    if constexpr (DIR) return rev ? T - 1 - s : s;
+    else return s;
+  }
+  // slot of hs / cs [row][T+1] holding the zero state, the state before step t and the state after it
+  __device__ __forceinline__ long zero_slot(long row, int T) const {
+    if constexpr (DIR) return row * (T + 1) + (rev ? T : 0);
+    else return row * (T + 1);
+  }
+  __device__ __forceinline__ long prev_slot(long row, int T, int t) const {
+    if constexpr (DIR) return row * (T + 1) + t + rev;
+    else return row * (T + 1) + t;
+  }
+  __device__ __forceinline__ long next_slot(long row, int T, int t) const {
+    if constexpr (DIR) return row * (T + 1) + t + 1 - rev;
+    else return row * (T + 1) + t + 1;
+  }
+  // element col of a y / dy sequence row (H wide when undirected) and of a last-state row
+  __device__ __forceinline__ long yseq(long row, int T, int s, int t, int H, int col) const {
+    if constexpr (DIR) return (row * T + (yproc ? s : t)) * ldy + yoff + col;
+    else return (row * T + t) * H + col;
+  }
+  __device__ __forceinline__ long ylast(long row, int H, int col) const {
+    if constexpr (DIR) return row * ldy + yoff + col;
+    else return row * H + col;
+  }
+  __device__ __forceinline__ float dyv(float v) const {
+    if constexpr (DIR) return dscale * v;
+    else return v;
+  }
+};
+
 __device__ __forceinline__ float hsig(float x) { return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f); }
 __device__ __forceinline__ float hsig_d(float y) { return (y > 0.f && y < 1.f) ? 0.2f : 0.f; }
 
 // ----------------------------------------------------------------------------- forward
-template <int CELL>  // 0 = GRU (gates z, r, h), 1 = LSTM (gates i, f, c, o), 2 = SimpleRNN (h)
+template <int CELL, bool DIR = false>  // 0 = GRU (gates z, r, h), 1 = LSTM (gates i, f, c, o), 2 = SimpleRNN (h)
 __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ xw, const float* __restrict__ U,
                                                       float* __restrict__ hs, float* __restrict__ cs,
                                                       float* __restrict__ gates, float* __restrict__ y, int B, int T,
-                                                      int H, int rs, int act, int ract) {
+                                                      int H, int rs, int act, int ract, const DirArg<DIR> dr) {
   constexpr int G = CELL == 0 ? 3 : (CELL == 1 ? 4 : 1);
   extern __shared__ float sm[];
   const int GH = G * H;
+  DirOf<DIR> dz;
+  if constexpr (DIR) {
+    const int d = blockIdx.y;
+    xw = dr.xw[d]; U = dr.U[d]; hs = dr.hs[d]; cs = dr.cs[d]; gates = dr.gates[d]; y = dr.y[d];
+    dz.load(dr, d);
+  }
   float* h = sm;              // [BB][H]
   float* c = h + BB * H;      // [BB][H]   (LSTM) / r*h (GRU)
   float* gb = c + BB * H;     // [BB][GH]  gate values of the current step
@@ -38,11 +101,12 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
   for (int i = threadIdx.x; i < BB * H; i += blockDim.x) h[i] = c[i] = 0.f;
   for (int i = threadIdx.x; i < nb * H; i += blockDim.x) {
     const int r = i / H, k = i - r * H;
-    hs[((long)(b0 + r) * (T + 1)) * H + k] = 0.f;
-    if (CELL == 1) cs[((long)(b0 + r) * (T + 1)) * H + k] = 0.f;
+    hs[dz.zero_slot((long)(b0 + r), T) * H + k] = 0.f;
+    if (CELL == 1) cs[dz.zero_slot((long)(b0 + r), T) * H + k] = 0.f;
   }
   __syncthreads();
-  for (int t = 0; t < T; ++t) {
+  for (int s = 0; s < T; ++s) {
+    const int t = dz.time(s, T);  // memory time index of processing step s
     // gate pre-activations x W + h U (GRU: only z, r here; the candidate needs r * h first)
     const int jend = CELL == 0 ? 2 * H : GH;
     for (int j = threadIdx.x; j < jend; j += blockDim.x) {
@@ -93,12 +157,12 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
         const float cn = g[H + k] * c[i] + g[k] * g[2 * H + k];
         c[i] = cn;
         hn = g[3 * H + k] * act_f(act, cn);
-        cs[((long)(b0 + r) * (T + 1) + t + 1) * H + k] = cn;
+        cs[dz.next_slot((long)(b0 + r), T, t) * H + k] = cn;
       }
       h[i] = hn;
-      hs[((long)(b0 + r) * (T + 1) + t + 1) * H + k] = hn;
-      if (rs) y[((long)(b0 + r) * T + t) * H + k] = hn;
-      else if (t == T - 1) y[(long)(b0 + r) * H + k] = hn;
+      hs[dz.next_slot((long)(b0 + r), T, t) * H + k] = hn;
+      if (rs) y[dz.yseq((long)(b0 + r), T, s, t, H, k)] = hn;
+      else if (s == T - 1) y[dz.ylast((long)(b0 + r), H, k)] = hn;
     }
     for (int i = threadIdx.x; i < nb * GH; i += blockDim.x) {
       const int r = i / GH, j = i - r * GH;
@@ -110,14 +174,21 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
 
 // ----------------------------------------------------------------------------- backward
 // UT = U^T [GH][H]; dgates [B][T][GH] = d(pre-activation)
-template <int CELL>
+template <int CELL, bool DIR = false>
 __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ UT,
                                                       const float* __restrict__ hs, const float* __restrict__ cs,
                                                       const float* __restrict__ gates, float* __restrict__ dgates,
-                                                      int B, int T, int H, int rs, int act, int ract) {
+                                                      int B, int T, int H, int rs, int act, int ract,
+                                                      const DirArg<DIR> dr) {
   constexpr int G = CELL == 0 ? 3 : (CELL == 1 ? 4 : 1);
   extern __shared__ float sm[];
   const int GH = G * H;
+  DirOf<DIR> dz;
+  if constexpr (DIR) {
+    const int d = blockIdx.y;
+    dy = dr.dy[d]; UT = dr.UT[d]; hs = dr.hs[d]; cs = dr.cs[d]; gates = dr.gates[d]; dgates = dr.dgates[d];
+    dz.load(dr, d);
+  }
   float* dh = sm;            // [BB][H] running dh (into h_t)
   float* aux = dh + BB * H;  // [BB][H] GRU: dh*z direct part; LSTM: running dc
   float* dp = aux + BB * H;  // [BB][GH] pre-activation gradients of the step
@@ -126,15 +197,16 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
   for (int i = threadIdx.x; i < BB * H; i += blockDim.x) dh[i] = aux[i] = 0.f;
   for (int i = threadIdx.x; i < BB * GH; i += blockDim.x) dp[i] = 0.f;
   __syncthreads();
-  for (int t = T - 1; t >= 0; --t) {
+  for (int s = T - 1; s >= 0; --s) {
+    const int t = dz.time(s, T);  // memory time index of processing step s
     for (int i = threadIdx.x; i < nb * H; i += blockDim.x) {
       const int r = i / H, k = i - r * H;
       const long row = (long)(b0 + r);
       float d = dh[i];
-      if (rs) d += dy[(row * T + t) * H + k];
-      else if (t == T - 1) d += dy[row * H + k];
+      if (rs) d += dz.dyv(dy[dz.yseq(row, T, s, t, H, k)]);
+      else if (s == T - 1) d += dz.dyv(dy[dz.ylast(row, H, k)]);
       const float* g = gates + (row * T + t) * GH;
-      const float hp = hs[(row * (T + 1) + t) * H + k];
+      const float hp = hs[dz.prev_slot(row, T, t) * H + k];
       float* p = dp + r * GH;
       if (CELL == 2) {
         p[k] = d * act_d(act, g[k]);
@@ -145,7 +217,7 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
         aux[i] = d * z;
       } else {
         const float gi = g[k], gf = g[H + k], gg = g[2 * H + k], go = g[3 * H + k];
-        const float cn = cs[(row * (T + 1) + t + 1) * H + k], cp = cs[(row * (T + 1) + t) * H + k];
+        const float cn = cs[dz.next_slot(row, T, t) * H + k], cp = cs[dz.prev_slot(row, T, t) * H + k];
         const float tc = act_f(act, cn);
         const float dc = aux[i] + d * go * act_d(act, tc);
         p[k] = dc * gg * act_d(ract, gi);
@@ -163,7 +235,7 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
         const float* p = dp + r * GH;
         float drh = 0.f;
         for (int j = 0; j < H; ++j) drh += p[2 * H + j] * UT[(long)(2 * H + j) * H + k];
-        const float hp = hs[(row * (T + 1) + t) * H + k];
+        const float hp = hs[dz.prev_slot(row, T, t) * H + k];
         const float rg = gates[(row * T + t) * GH + H + k];
         dp[r * GH + H + k] = drh * hp * act_d(ract, rg);
         aux[i] += drh * rg;
@@ -240,11 +312,14 @@ constexpr int bwd_threads() { return H * (((CELL == 0 ? 3 : 4) * H / 64) <= 4 ? 
 
 // REP: replica-batched (RnnRep): the workgroup's replica is b0 / rp.B; W / U / bias come from its table
 // entries and x from its resident shard at mini-batch (*rp.ctr % rp.nbr[r]) — outputs stay global-row indexed.
-template <int CELL, int H, int BB_, bool FUSE, bool REP = false>
+// DIR: directed (RnnDir): blockIdx.y is the direction; xw / W / bias / U / hs / cs / gates / y come from its table entry.
+template <int CELL, int H, int BB_, bool FUSE, bool REP = false, bool DIR = false>
 __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     const float* __restrict__ xw, const float* __restrict__ x, const float* __restrict__ W,
     const float* __restrict__ bias, int I, const float* __restrict__ U, float* __restrict__ hs,
-    float* __restrict__ cs, float* __restrict__ gates, float* __restrict__ y, int B, int T, int rs, const RnnRep rp) {
+    float* __restrict__ cs, float* __restrict__ gates, float* __restrict__ y, int B, int T, int rs,
+    const RegArg<DIR> rp) {
+  static_assert(!(REP && DIR), "replica batching is forward-only");
   constexpr int G = CELL == 0 ? 3 : 4;
   constexpr int GH = G * H;
   constexpr int KS = H / CH;
@@ -266,6 +341,13 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     x = rp.x[r];
     xrow0 = (long)(*rp.ctr % rp.nbr[r]) * rp.B + (b0 - r * rp.B);
   }
+  DirOf<DIR> dz;
+  if constexpr (DIR) {
+    const int d = blockIdx.y;
+    xw = rp.xw[d]; W = rp.W[d]; bias = rp.b[d]; U = rp.U[d];
+    hs = rp.hs[d]; cs = rp.cs[d]; gates = rp.gates[d]; y = rp.y[d];
+    dz.load(rp, d);
+  }
   float u[CH];
 #pragma unroll
   for (int i = 0; i < CH; ++i) u[i] = U[(long)(kh * CH + i) * GH + j];
@@ -280,8 +362,8 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
   // branch and wait per element); padded inputs meet wv = 0.
   int zoff;
   asm volatile("v_mov_b32 %0, 0" : "=v"(zoff));
-  auto fetch_x = [&](int t, float (&xr)[BB_][IMAX]) {
-    const int tc = min(max(t, 0), T - 1);
+  auto fetch_x = [&](int s, float (&xr)[BB_][IMAX]) {
+    const int tc = min(max(dz.time(s, T), 0), T - 1);  // processing step -> memory time index first, then the clamp
 #pragma unroll
     for (int r = 0; r < BB_; ++r) {
       const long bt = (xrow0 + min(r, nb - 1)) * T + tc;
@@ -312,8 +394,8 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
   const bool eown = er < nb;
   const long erow = b0 + er;
   if (eown) {
-    hs[(erow * (T + 1)) * H + ek] = 0.f;
-    if (CELL == 1) cs[(erow * (T + 1)) * H + ek] = 0.f;
+    hs[dz.zero_slot(erow, T) * H + ek] = 0.f;
+    if (CELL == 1) cs[dz.zero_slot(erow, T) * H + ek] = 0.f;
   }
   float xr[BB_][IMAX], xv[BB_];
   fetch_x(0, xr);
@@ -336,8 +418,9 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
       for (int r = 0; r < BB_; ++r) acc[r] += xor_lane<1>(acc[r]);
     }
   };
-  for (int t = 0; t < T; ++t) {
-    fetch_x(t + 1, xr);  // the next step's inputs (consumed at the end of this step)
+  for (int s = 0; s < T; ++s) {
+    const int t = dz.time(s, T);  // memory time index of processing step s
+    fetch_x(s + 1, xr);  // the next step's inputs (consumed at the end of this step)
     float acc[BB_];
     if (CELL == 1 || j < 2 * H) {  // wave-uniform: 2H columns span whole waves
       contract(h, acc);
@@ -378,12 +461,12 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
         const float cn = gb[er][H + ek] * c[er][cpos(ek)] + gb[er][ek] * gb[er][2 * H + ek];
         c[er][cpos(ek)] = cn;
         hn = gb[er][3 * H + ek] * tanhf(cn);
-        cs[(erow * (T + 1) + t + 1) * H + ek] = cn;
+        cs[dz.next_slot(erow, T, t) * H + ek] = cn;
       }
       h[er][cpos(ek)] = hn;
-      hs[(erow * (T + 1) + t + 1) * H + ek] = hn;
-      if (rs) y[(erow * T + t) * H + ek] = hn;
-      else if (t == T - 1) y[erow * H + ek] = hn;
+      hs[dz.next_slot(erow, T, t) * H + ek] = hn;
+      if (rs) y[dz.yseq(erow, T, s, t, H, ek)] = hn;
+      else if (s == T - 1) y[dz.ylast(erow, H, ek)] = hn;
     }
     for (int i = tid; i < nb * GH; i += NT) {
       const int r = i / GH, jj = i - r * GH;
@@ -395,11 +478,12 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
   }
 }
 
-template <int CELL, int H, int BB_, bool REP = false>
+template <int CELL, int H, int BB_, bool REP = false, bool DIR = false>
 __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
     const float* __restrict__ dy, const float* __restrict__ U, const float* __restrict__ hs,
     const float* __restrict__ cs, const float* __restrict__ gates, float* __restrict__ dgates, int B, int T, int rs,
-    const RnnRep rp) {
+    const RegArg<DIR> rp) {
+  static_assert(!(REP && DIR), "replica batching is forward-only");
   constexpr int G = CELL == 0 ? 3 : 4;
   constexpr int GH = G * H;
   constexpr int JS = GH / CH;                            // column chunks
@@ -417,6 +501,12 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
   const int b0 = blockIdx.x * BB_;
   const int nb = min(BB_, B - b0);
   if constexpr (REP) U = rp.U[b0 / rp.B];
+  DirOf<DIR> dz;
+  if constexpr (DIR) {
+    const int d = blockIdx.y;
+    dy = rp.dy[d]; U = rp.U[d]; hs = rp.hs[d]; cs = rp.cs[d]; gates = rp.gates[d]; dgates = rp.dgates[d];
+    dz.load(rp, d);
+  }
   float u[CH];
 #pragma unroll
   for (int i = 0; i < CH; i += 4) {
@@ -430,17 +520,18 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
   const bool eown = er < nb;
   const long erow = b0 + er;
   struct In { float d, g0, g1, g2, g3, hp, cn, cp; };
-  auto load_in = [&](int t, In& v) {
-    if (!eown || t < 0) return;
-    v.d = rs ? dy[(erow * T + t) * H + ek] : (t == T - 1 ? dy[erow * H + ek] : 0.f);
+  auto load_in = [&](int s, In& v) {
+    if (!eown || s < 0) return;  // the guard is on the processing step; every index below is then in range
+    const int t = dz.time(s, T);
+    v.d = rs ? dz.dyv(dy[dz.yseq(erow, T, s, t, H, ek)]) : (s == T - 1 ? dz.dyv(dy[dz.ylast(erow, H, ek)]) : 0.f);
     const float* g = gates + (erow * T + t) * GH;
     v.g0 = g[ek]; v.g1 = g[H + ek]; v.g2 = g[2 * H + ek];
     if (CELL == 1) {
       v.g3 = g[3 * H + ek];
-      v.cn = cs[(erow * (T + 1) + t + 1) * H + ek];
-      v.cp = cs[(erow * (T + 1) + t) * H + ek];
+      v.cn = cs[dz.next_slot(erow, T, t) * H + ek];
+      v.cp = cs[dz.prev_slot(erow, T, t) * H + ek];
     } else {
-      v.hp = hs[(erow * (T + 1) + t) * H + ek];
+      v.hp = hs[dz.prev_slot(erow, T, t) * H + ek];
     }
   };
   In cur{}, nxt{};
@@ -470,8 +561,9 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
       if constexpr (JSP == 8) acc[r] += other_quad(acc[r]);
     }
   };
-  for (int t = T - 1; t >= 0; --t) {
-    load_in(t - 1, nxt);  // prefetch the previous step's saved activations
+  for (int s = T - 1; s >= 0; --s) {
+    const int t = dz.time(s, T);  // memory time index of processing step s
+    load_in(s - 1, nxt);  // prefetch the previous step's saved activations
     if (eown) {
       const float d = dh[er][ek] + cur.d;
       float* pr = p[er];
@@ -532,7 +624,8 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
 // chunk of PG_BT (b,t) rows staged in LDS; 256 threads x 4x4 outputs.
 constexpr int PG_BT = 128;
 
-template <int CELL>
+// REV: saved tensors of a reverse-direction recurrence, h_{t-1} in slot t + 1
+template <int CELL, bool REV = false>
 __global__ __launch_bounds__(256) void rnn_param_grad_kernel(const float* __restrict__ dg, const float* __restrict__ hs,
                                                              const float* __restrict__ gates,
                                                              const float* __restrict__ x, float* __restrict__ gU,
@@ -558,7 +651,7 @@ __global__ __launch_bounds__(256) void rnn_param_grad_kernel(const float* __rest
     const int m = m0 + c;
     float a = 0.f;
     if (m < H) {
-      a = hs[(b * (T + 1) + t) * H + m];
+      a = hs[(b * (T + 1) + t + (REV ? 1 : 0)) * H + m];
       if (cand) a *= gates[bt * GH + H + m];
     } else if (m < H + I) {
       a = x[bt * I + (m - H)];
@@ -622,6 +715,37 @@ int launch_bwd_reg(const float* dy, const float* U, const float* hs, const float
   return (int)hipGetLastError();
 }
 
+// directed launches: grid.y = direction, everything per direction comes from the table
+template <int CELL, int H, int BB_>
+int launch_fwd_reg_dir(const RnnDir& d, int ndir, const float* x, int I, int B, int T, int rs, hipStream_t s) {
+  const bool fuse = !d.xw[0];
+  if (fuse && (I < 1 || I > IMAX)) return (int)hipErrorInvalidValue;
+  const dim3 grid((B + BB_ - 1) / BB_, ndir), block(fwd_threads<CELL, H>());
+  const float* const np = nullptr;
+  float* const nq = nullptr;
+  if (fuse)
+    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, true, false, true>), grid, block, 0, s, np, x, np, np, I, np,
+                       nq, nq, nq, nq, B, T, rs, d);
+  else
+    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, false, false, true>), grid, block, 0, s, np, x, np, np, I, np,
+                       nq, nq, nq, nq, B, T, rs, d);
+  return (int)hipGetLastError();
+}
+
+template <int CELL, int H, int BB_>
+int launch_bwd_reg_dir(const RnnDir& d, int ndir, int B, int T, int rs, hipStream_t s) {
+  const dim3 grid((B + BB_ - 1) / BB_, ndir);
+  const float* const np = nullptr;
+  hipLaunchKernelGGL((rnn_bwd_reg_kernel<CELL, H, BB_, false, true>), grid, dim3(bwd_threads<CELL, H>()), 0, s, np, np,
+                     np, np, np, (float*)nullptr, B, T, rs, d);
+  return (int)hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void bidir_merge_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                          float* __restrict__ out, long n, float scale) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = scale * (a[i] + b[i]);
+}
+
 }  // namespace
 
 bool rnn_fast_path(int H) { return H == 128 || H == 64; }
@@ -647,23 +771,32 @@ int rnn_fwd(int cell, const float* xw, const float* x, const float* W, const flo
   const int threads = std::min(512, ((G * H + 63) / 64) * 64);
   const dim3 grid((B + BB - 1) / BB);
   if (cell == 0)
-    hipLaunchKernelGGL(rnn_fwd_kernel<0>, grid, dim3(threads), lds, s, xw, U, hs, cs, gates, y, B, T, H, rs, act, ract);
+    hipLaunchKernelGGL(rnn_fwd_kernel<0>, grid, dim3(threads), lds, s, xw, U, hs, cs, gates, y, B, T, H, rs, act, ract, NoDir{});
   else if (cell == 1)
-    hipLaunchKernelGGL(rnn_fwd_kernel<1>, grid, dim3(threads), lds, s, xw, U, hs, cs, gates, y, B, T, H, rs, act, ract);
+    hipLaunchKernelGGL(rnn_fwd_kernel<1>, grid, dim3(threads), lds, s, xw, U, hs, cs, gates, y, B, T, H, rs, act, ract, NoDir{});
   else
-    hipLaunchKernelGGL(rnn_fwd_kernel<2>, grid, dim3(threads), lds, s, xw, U, hs, cs, gates, y, B, T, H, rs, act, ract);
+    hipLaunchKernelGGL(rnn_fwd_kernel<2>, grid, dim3(threads), lds, s, xw, U, hs, cs, gates, y, B, T, H, rs, act, ract, NoDir{});
   return (int)hipGetLastError();
 }
 
 bool rnn_bwd_uses_ut(int H) { return !rnn_fast_path(H); }
 
 int rnn_param_grad(int cell, const float* dg, const float* hs, const float* gates, const float* x, float* gU,
-                   float* gW, float* gb, int B, int T, int H, int I, hipStream_t s) {
+                   float* gW, float* gb, int B, int T, int H, int I, hipStream_t s, int rev) {
   const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
   if (cell == 0 && (2 * H) % 64) return (int)hipErrorInvalidValue;  // candidate columns start on a tile
   const int M = H + I + (gb ? 1 : 0);
   const long BT = (long)B * T;
   const dim3 grid((M + 63) / 64, (G * H + 63) / 64, (unsigned)((BT + PG_BT - 1) / PG_BT));
+  if (rev) {
+    if (cell == 0)
+      hipLaunchKernelGGL((rnn_param_grad_kernel<0, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+    else if (cell == 1)
+      hipLaunchKernelGGL((rnn_param_grad_kernel<1, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+    else
+      hipLaunchKernelGGL((rnn_param_grad_kernel<2, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+    return (int)hipGetLastError();
+  }
   if (cell == 0)
     hipLaunchKernelGGL(rnn_param_grad_kernel<0>, grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
   else if (cell == 1)
@@ -688,13 +821,75 @@ int rnn_bwd(int cell, const float* dy, const float* U, const float* UT, const fl
   const dim3 grid((B + BB - 1) / BB);
   if (cell == 0)
     hipLaunchKernelGGL(rnn_bwd_kernel<0>, grid, dim3(threads), lds, s, dy, UT, hs, cs, gates, dgates, B, T, H, rs, act,
-                       ract);
+                       ract, NoDir{});
   else if (cell == 1)
     hipLaunchKernelGGL(rnn_bwd_kernel<1>, grid, dim3(threads), lds, s, dy, UT, hs, cs, gates, dgates, B, T, H, rs, act,
-                       ract);
+                       ract, NoDir{});
   else
     hipLaunchKernelGGL(rnn_bwd_kernel<2>, grid, dim3(threads), lds, s, dy, UT, hs, cs, gates, dgates, B, T, H, rs, act,
-                       ract);
+                       ract, NoDir{});
+  return (int)hipGetLastError();
+}
+
+int rnn_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
+                int ract, hipStream_t s) {
+  if (ndir < 1 || ndir > 2 || (ndir == 2 && !d.xw[0] != !d.xw[1])) return (int)hipErrorInvalidValue;
+  const bool reg = rnn_reg_path(cell, H, act, ract);
+  if (reg && H == 128)
+    return cell == 0 ? launch_fwd_reg_dir<0, 128, RNN_BB_FWD>(d, ndir, x, I, B, T, rs, s)
+                     : launch_fwd_reg_dir<1, 128, RNN_BB_FWD>(d, ndir, x, I, B, T, rs, s);
+  if (reg && H == 64)
+    return cell == 0 ? launch_fwd_reg_dir<0, 64, 2>(d, ndir, x, I, B, T, rs, s)
+                     : launch_fwd_reg_dir<1, 64, 2>(d, ndir, x, I, B, T, rs, s);
+  if (!d.xw[0]) return (int)hipErrorInvalidValue;  // generic kernels need the projection precomputed
+  const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
+  const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
+  const int threads = std::min(512, ((G * H + 63) / 64) * 64);
+  const dim3 grid((B + BB - 1) / BB, ndir);
+  const float* const np = nullptr;
+  float* const nq = nullptr;
+  if (cell == 0)
+    hipLaunchKernelGGL((rnn_fwd_kernel<0, true>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H, rs, act,
+                       ract, d);
+  else if (cell == 1)
+    hipLaunchKernelGGL((rnn_fwd_kernel<1, true>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H, rs, act,
+                       ract, d);
+  else
+    hipLaunchKernelGGL((rnn_fwd_kernel<2, true>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H, rs, act,
+                       ract, d);
+  return (int)hipGetLastError();
+}
+
+int rnn_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract, hipStream_t s) {
+  if (ndir < 1 || ndir > 2) return (int)hipErrorInvalidValue;
+  const bool reg = rnn_reg_path(cell, H, act, ract);
+  if (reg && H == 128)
+    return cell == 0 ? launch_bwd_reg_dir<0, 128, RNN_BB_BWD>(d, ndir, B, T, rs, s)
+                     : launch_bwd_reg_dir<1, 128, RNN_BB_BWD>(d, ndir, B, T, rs, s);
+  if (reg && H == 64)
+    return cell == 0 ? launch_bwd_reg_dir<0, 64, 2>(d, ndir, B, T, rs, s)
+                     : launch_bwd_reg_dir<1, 64, 2>(d, ndir, B, T, rs, s);
+  const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
+  const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
+  const int threads = std::min(512, ((G * H + 63) / 64) * 64);
+  const dim3 grid((B + BB - 1) / BB, ndir);
+  const float* const np = nullptr;
+  if (cell == 0)
+    hipLaunchKernelGGL((rnn_bwd_kernel<0, true>), grid, dim3(threads), lds, s, np, np, np, np, np, (float*)nullptr, B, T,
+                       H, rs, act, ract, d);
+  else if (cell == 1)
+    hipLaunchKernelGGL((rnn_bwd_kernel<1, true>), grid, dim3(threads), lds, s, np, np, np, np, np, (float*)nullptr, B, T,
+                       H, rs, act, ract, d);
+  else
+    hipLaunchKernelGGL((rnn_bwd_kernel<2, true>), grid, dim3(threads), lds, s, np, np, np, np, np, (float*)nullptr, B, T,
+                       H, rs, act, ract, d);
+  return (int)hipGetLastError();
+}
+
+int bidir_merge(const float* a, const float* b, float* out, long n, float scale, hipStream_t s) {
+  if (n <= 0) return 0;
+  const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 1024);
+  hipLaunchKernelGGL(bidir_merge_kernel, dim3(blocks), dim3(256), 0, s, a, b, out, n, scale);
   return (int)hipGetLastError();
 }
 

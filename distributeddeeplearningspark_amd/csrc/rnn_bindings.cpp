@@ -28,10 +28,235 @@ void f32mm(const at::Tensor& a, long sam, long sak, const at::Tensor& b, long sb
   TORCH_CHECK(e == 0, "gemm_f32 launch failed: ", hipGetErrorString((hipError_t)e));
 }
 
+// ------------------------------------------------------------------------------------------------
+// Directed recurrences (go_backwards / Bidirectional; RnnDir in ddl_ops.h): ndir = 1 or 2 directions over the
+// same x in ONE recurrence launch per pass.  merge: 0 none (one direction), 1 concat, 2 sum, 3 ave.
+// Saved tensors are stacked over the direction: hs / cs [ndir][B][T+1][H], gates [ndir][B][T][GH].
+struct DirWeights {
+  at::Tensor W, U, b;  // b undefined: no bias
+};
+
+std::vector<DirWeights> dir_weights(const py::list& Ws, const py::list& Us, const py::list& bs, int64_t I, int64_t G) {
+  const size_t nd = Ws.size();
+  TORCH_CHECK((nd == 1 || nd == 2) && Us.size() == nd && bs.size() == nd, "rnn: one or two directions");
+  std::vector<DirWeights> out(nd);
+  for (size_t d = 0; d < nd; ++d) {
+    out[d].W = Ws[d].cast<at::Tensor>().contiguous();
+    out[d].U = Us[d].cast<at::Tensor>().contiguous();
+    if (!bs[d].is_none()) out[d].b = bs[d].cast<at::Tensor>().contiguous();
+    const int64_t H = out[0].U.size(0);
+    for (const at::Tensor* t : {&out[d].W, &out[d].U})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat, "rnn: fp32 GPU weights");
+    TORCH_CHECK(out[d].W.size(0) == I && out[d].W.size(1) == G * H && out[d].U.size(0) == H && out[d].U.size(1) == G * H,
+                "rnn: W [I,GH], U [H,GH] (equal shapes in both directions)");
+    TORCH_CHECK(!out[d].b.defined() || (out[d].b.scalar_type() == at::kFloat && out[d].b.numel() == G * H),
+                "rnn: bias [GH] fp32");
+    TORCH_CHECK(out[d].b.defined() == out[0].b.defined(), "rnn: both directions with or without bias");
+  }
+  return out;
+}
+
+int merge_id(const std::string& m) {
+  TORCH_CHECK(m == "concat" || m == "sum" || m == "ave", "birnn: merge_mode must be 'concat', 'sum' or 'ave'");
+  return m == "concat" ? 1 : (m == "sum" ? 2 : 3);
+}
+
+py::tuple dir_fwd(int c, const at::Tensor& x, const std::vector<DirWeights>& w, const std::vector<int>& rev, bool rs,
+                  int merge, bool yproc, int64_t act, int64_t ract) {
+  const int G = gates_of(c);
+  const int nd = (int)w.size();
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
+  const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = w[0].U.size(0);
+  TORCH_CHECK(T >= 1, "rnn_fwd: empty sequence");
+  at::DeviceGuard g(x.device());
+  at::Tensor xc = x.contiguous();
+  auto opt = x.options();
+  at::Tensor xw;
+  const bool reg = rnn_reg_path(c, (int)H, (int)act, (int)ract);
+  if (!(reg && rnn_fuses_input((int)H, (int)I))) {  // one projection GEMM per direction
+    xw = at::empty({nd, B * T, G * H}, opt);
+    for (int d = 0; d < nd; ++d) {
+      at::Tensor xwd = xw.select(0, d);
+      f32mm(xc, I, 1, w[d].W, G * H, 1, xwd, G * H, B * T, G * H, I, 0.f,
+            w[d].b.defined() ? w[d].b.data_ptr<float>() : nullptr);
+    }
+  }
+  at::Tensor hs = at::empty({nd, B, T + 1, H}, opt);
+  at::Tensor cs = c == 1 ? at::empty({nd, B, T + 1, H}, opt) : at::empty({0}, opt);
+  at::Tensor gates = at::empty({nd, B, T, G * H}, opt);
+  const int64_t Hy = merge == 1 ? 2 * H : H;  // output width
+  at::Tensor y = rs ? at::empty({B, T, Hy}, opt) : at::empty({B, Hy}, opt);
+  at::Tensor parts;  // sum / ave: the two directions' outputs, merged below
+  if (merge >= 2) parts = at::empty({2, y.numel()}, opt);
+  RnnDir dr{};
+  for (int d = 0; d < nd; ++d) {
+    dr.xw[d] = xw.defined() ? xw.data_ptr<float>() + d * B * T * G * H : nullptr;
+    dr.W[d] = w[d].W.data_ptr<float>();
+    dr.b[d] = w[d].b.defined() ? w[d].b.data_ptr<float>() : nullptr;
+    dr.U[d] = w[d].U.data_ptr<float>();
+    dr.hs[d] = hs.data_ptr<float>() + d * B * (T + 1) * H;
+    dr.cs[d] = c == 1 ? cs.data_ptr<float>() + d * B * (T + 1) * H : nullptr;
+    dr.gates[d] = gates.data_ptr<float>() + d * B * T * G * H;
+    dr.y[d] = merge >= 2 ? parts.data_ptr<float>() + d * y.numel() : y.data_ptr<float>();
+    dr.rev[d] = rev[d];
+    dr.yoff[d] = merge == 1 ? d * (int)H : 0;
+    dr.yproc[d] = yproc ? 1 : 0;
+  }
+  dr.ldy = (int)Hy;
+  dr.dscale = 1.f;
+  int e = rnn_fwd_dir(c, dr, nd, xc.data_ptr<float>(), (int)I, (int)B, (int)T, (int)H, rs ? 1 : 0, (int)act, (int)ract,
+                      cur_stream());
+  TORCH_CHECK(e == 0, "rnn_fwd launch failed: ", hipGetErrorString((hipError_t)e));
+  if (merge >= 2) {
+    e = bidir_merge(parts.data_ptr<float>(), parts.data_ptr<float>() + y.numel(), y.data_ptr<float>(), y.numel(),
+                    merge == 3 ? 0.5f : 1.f, cur_stream());
+    TORCH_CHECK(e == 0, "bidir_merge launch failed: ", hipGetErrorString((hipError_t)e));
+  }
+  py::list saved;
+  saved.append(hs);
+  saved.append(cs);
+  saved.append(gates);
+  return py::make_tuple(y, saved);
+}
+
+// one direction's parameter gradients from its dgates: accumulated into the given fp32 buffers (returns Nones) or
+// returned in fresh ones
+py::tuple dir_param_grads(int c, const at::Tensor& dg, const at::Tensor& hs, const at::Tensor& gates,
+                          const at::Tensor& xc, bool has_b, int rev, const at::Tensor& gW, const at::Tensor& gU,
+                          const at::Tensor& gb, int64_t B, int64_t T, int64_t I, int64_t H) {
+  const int G = gates_of(c);
+  const bool tiles = c != 0 || (2 * H) % 64 == 0;
+  if (tiles && gU.defined() && gW.defined() && gb.defined() == has_b) {
+    for (const at::Tensor* t : {&gU, &gW})
+      TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous(), "rnn_bwd: fp32 contiguous grad buffers");
+    TORCH_CHECK(gU.numel() == H * G * H && gW.numel() == I * G * H, "rnn_bwd: grad buffer sizes");
+    if (has_b) TORCH_CHECK(gb.scalar_type() == at::kFloat && gb.numel() == G * H, "rnn_bwd: bias grad buffer");
+    const int e = rnn_param_grad(c, dg.data_ptr<float>(), hs.data_ptr<float>(), gates.data_ptr<float>(),
+                                 xc.data_ptr<float>(), gU.data_ptr<float>(), gW.data_ptr<float>(),
+                                 has_b ? gb.data_ptr<float>() : nullptr, (int)B, (int)T, (int)H, (int)I, cur_stream(), rev);
+    TORCH_CHECK(e == 0, "rnn_param_grad launch failed: ", hipGetErrorString((hipError_t)e));
+    return py::make_tuple(py::none(), py::none(), py::none());
+  }
+  at::Tensor dW = at::zeros({I, G * H}, xc.options());
+  at::Tensor dU = at::zeros({H, G * H}, xc.options());
+  at::Tensor db = has_b ? at::zeros({G * H}, xc.options()) : at::Tensor();
+  if (tiles) {
+    const int e = rnn_param_grad(c, dg.data_ptr<float>(), hs.data_ptr<float>(), gates.data_ptr<float>(),
+                                 xc.data_ptr<float>(), dU.data_ptr<float>(), dW.data_ptr<float>(),
+                                 has_b ? db.data_ptr<float>() : nullptr, (int)B, (int)T, (int)H, (int)I, cur_stream(), rev);
+    TORCH_CHECK(e == 0, "rnn_param_grad launch failed: ", hipGetErrorString((hipError_t)e));
+  } else {
+    // GRU with 2H not a multiple of 64 (as rnn_bwd_): h_{t-1} is slot t + rev of the saved sequence
+    at::Tensor hp = hs.narrow(1, rev, T).contiguous().view({B * T, H});
+    at::Tensor rh = gates.view({B * T, G * H}).narrow(1, H, H).mul(hp).contiguous();
+    f32mm(xc, 1, I, dg, G * H, 1, dW, G * H, I, G * H, B * T);
+    f32mm(hp, 1, H, dg, G * H, 1, dU, G * H, H, 2 * H, B * T);
+    at::Tensor dUh = dU.narrow(1, 2 * H, H);
+    at::Tensor dgh = dg.narrow(1, 2 * H, H);
+    const int e2 = gemm_f32(rh.data_ptr<float>(), 1, H, dgh.data_ptr<float>(), G * H, 1, dUh.data_ptr<float>(), G * H,
+                            (int)H, (int)H, (int)(B * T), 1.f, 0.f, nullptr, 0, cur_stream());
+    TORCH_CHECK(e2 == 0, "gemm_f32 launch failed");
+    if (has_b) {
+      const int e3 = colsum_f32(dg.data_ptr<float>(), db.data_ptr<float>(), B * T, (int)(G * H), cur_stream());
+      TORCH_CHECK(e3 == 0, "colsum_f32 launch failed");
+    }
+  }
+  return py::make_tuple(dW, dU, db.defined() ? py::cast(db) : py::none());
+}
+
+// Returns (dx | None, [(dW, dU, db) per direction]) with None for what went into the given gradient buffers.
+py::tuple dir_bwd(int c, const at::Tensor& dy, const at::Tensor& x, const std::vector<DirWeights>& w,
+                  const std::vector<int>& rev, bool rs, int merge, bool yproc, const std::vector<at::Tensor>& saved,
+                  const std::vector<DirWeights>& gr, bool need_dx, int64_t act, int64_t ract) {
+  const int G = gates_of(c);
+  const int nd = (int)w.size();
+  const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = w[0].U.size(0);
+  const bool reg = rnn_reg_path(c, (int)H, (int)act, (int)ract);
+  TORCH_CHECK(saved.size() == 3, "rnn_bwd: saved = [hs, cs, gates]");
+  const at::Tensor& hs = saved[0];
+  const at::Tensor& cs = saved[1];
+  const at::Tensor& gates = saved[2];
+  TORCH_CHECK(hs.numel() == nd * B * (T + 1) * H && gates.numel() == nd * B * T * G * H &&
+                  (c != 1 || cs.numel() == hs.numel()), "rnn_bwd: saved tensor sizes");
+  const int64_t Hy = merge == 1 ? 2 * H : H;
+  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kFloat && dy.numel() == (rs ? B * T * Hy : B * Hy),
+              "rnn_bwd: dy does not match the output");
+  at::DeviceGuard g(x.device());
+  at::Tensor dyc = dy.contiguous(), xc = x.contiguous();
+  at::Tensor UT;
+  if (!reg) {  // the generic kernels read U^T [GH][H]
+    UT = at::empty({nd, G * H, H}, x.options());
+    for (int d = 0; d < nd; ++d) {
+      const int et = transpose_f32(w[d].U.data_ptr<float>(), UT.data_ptr<float>() + d * G * H * H, (int)H, (int)(G * H),
+                                   cur_stream());
+      TORCH_CHECK(et == 0, "transpose_f32 launch failed");
+    }
+  }
+  at::Tensor dgates = at::empty({nd, B * T, G * H}, x.options());
+  RnnDir dr{};
+  for (int d = 0; d < nd; ++d) {
+    dr.U[d] = w[d].U.data_ptr<float>();
+    dr.UT[d] = UT.defined() ? UT.data_ptr<float>() + d * G * H * H : nullptr;
+    dr.hs[d] = hs.data_ptr<float>() + d * B * (T + 1) * H;
+    dr.cs[d] = c == 1 ? cs.data_ptr<float>() + d * B * (T + 1) * H : nullptr;
+    dr.gates[d] = gates.data_ptr<float>() + d * B * T * G * H;
+    dr.dgates[d] = dgates.data_ptr<float>() + d * B * T * G * H;
+    dr.dy[d] = dyc.data_ptr<float>();
+    dr.rev[d] = rev[d];
+    dr.yoff[d] = merge == 1 ? d * (int)H : 0;
+    dr.yproc[d] = yproc ? 1 : 0;
+  }
+  dr.ldy = (int)Hy;
+  dr.dscale = merge == 3 ? 0.5f : 1.f;
+  const int e = rnn_bwd_dir(c, dr, nd, (int)B, (int)T, (int)H, rs ? 1 : 0, (int)act, (int)ract, cur_stream());
+  TORCH_CHECK(e == 0, "rnn_bwd launch failed: ", hipGetErrorString((hipError_t)e));
+  py::object dx = py::none();
+  if (need_dx) {  // dx[bt][i] = sum_d sum_j dg_d[bt][j] W_d[i][j]: the second direction accumulates
+    at::Tensor dxt = at::empty({B * T, I}, x.options());
+    for (int d = 0; d < nd; ++d) f32mm(dgates.select(0, d), G * H, 1, w[d].W, 1, G * H, dxt, I, B * T, I, G * H, d ? 1.f : 0.f);
+    dx = py::cast(dxt.view({B, T, I}));
+  }
+  py::list pg;
+  for (int d = 0; d < nd; ++d)
+    pg.append(dir_param_grads(c, dgates.select(0, d), hs.select(0, d), gates.select(0, d), xc, w[d].b.defined(), rev[d],
+                              gr[d].W, gr[d].U, gr[d].b, B, T, I, H));
+  return py::make_tuple(dx, pg);
+}
+
+at::Tensor opt_tensor(const py::handle& o) { return o.is_none() ? at::Tensor() : o.cast<at::Tensor>(); }
+
+py::tuple birnn_fwd_(const std::string& cell, const at::Tensor& x, py::list Ws, py::list Us, py::list bs, bool rs,
+                     const std::string& merge, int64_t act, int64_t ract) {
+  const int c = cell_id(cell);
+  TORCH_CHECK(Ws.size() == 2, "birnn_fwd: [forward, backward] weights");
+  return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), gates_of(c)), {0, 1}, rs, merge_id(merge), false, act, ract);
+}
+
+py::tuple birnn_bwd_(const std::string& cell, const at::Tensor& dy, const at::Tensor& x, py::list Ws, py::list Us,
+                     py::list bs, bool rs, const std::string& merge, std::vector<at::Tensor> saved, py::list gWs,
+                     py::list gUs, py::list gbs, bool need_dx, int64_t act, int64_t ract) {
+  const int c = cell_id(cell);
+  TORCH_CHECK(Ws.size() == 2 && gWs.size() == 2 && gUs.size() == 2 && gbs.size() == 2,
+              "birnn_bwd: [forward, backward] weights and gradient buffers");
+  std::vector<DirWeights> gr(2);
+  for (int d = 0; d < 2; ++d) gr[d] = {opt_tensor(gWs[d]), opt_tensor(gUs[d]), opt_tensor(gbs[d])};
+  return dir_bwd(c, dy, x, dir_weights(Ws, Us, bs, x.size(2), gates_of(c)), {0, 1}, rs, merge_id(merge), false, saved,
+                 gr, need_dx, act, ract);
+}
+
+// reverse: the sequence is processed last-to-first (go_backwards).  y_input_order: a returned sequence (and its
+// gradient) is in input time order; default is Keras' processing order.  Both default to the forward layer.
 py::tuple rnn_fwd_(const std::string& cell, const at::Tensor& x, const at::Tensor& W, const at::Tensor& U,
-                   c10::optional<at::Tensor> b, bool rs, int64_t act, int64_t ract) {
+                   c10::optional<at::Tensor> b, bool rs, int64_t act, int64_t ract, bool reverse, bool y_input_order) {
   const int c = cell_id(cell);
   const int G = gates_of(c);
+  if (reverse) {
+    py::list Ws, Us, bs;
+    Ws.append(W);
+    Us.append(U);
+    bs.append(b ? py::cast(*b) : py::none());
+    return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), G), {1}, rs, 0, !y_input_order, act, ract);
+  }
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
   const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = U.size(0);
   TORCH_CHECK(W.size(0) == I && W.size(1) == G * H && U.size(1) == G * H, "rnn_fwd: W [I,GH], U [H,GH]");
@@ -69,9 +294,21 @@ py::tuple rnn_fwd_(const std::string& cell, const at::Tensor& x, const at::Tenso
 py::tuple rnn_bwd_(const std::string& cell, const at::Tensor& dy, const at::Tensor& x, const at::Tensor& W,
                    const at::Tensor& U, c10::optional<at::Tensor> b, bool rs, std::vector<at::Tensor> saved,
                    c10::optional<at::Tensor> gW, c10::optional<at::Tensor> gU, c10::optional<at::Tensor> gb,
-                   bool need_dx, int64_t act, int64_t ract) {
+                   bool need_dx, int64_t act, int64_t ract, bool reverse, bool y_input_order) {
   const int c = cell_id(cell);
   const int G = gates_of(c);
+  if (reverse) {
+    py::list Ws, Us, bs;
+    Ws.append(W);
+    Us.append(U);
+    bs.append(b ? py::cast(*b) : py::none());
+    std::vector<DirWeights> gr(1);
+    gr[0] = {gW ? *gW : at::Tensor(), gU ? *gU : at::Tensor(), gb ? *gb : at::Tensor()};
+    py::tuple r = dir_bwd(c, dy, x, dir_weights(Ws, Us, bs, x.size(2), G), {1}, rs, 0, !y_input_order, saved, gr,
+                          need_dx, act, ract);
+    py::tuple pg = r[1].cast<py::list>()[0].cast<py::tuple>();
+    return py::make_tuple(r[0], pg[0], pg[1], pg[2]);
+  }
   const bool reg = rnn_reg_path(c, (int)U.size(0), (int)act, (int)ract);
   const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = U.size(0);
   TORCH_CHECK(saved.size() == 3, "rnn_bwd: saved = [hs, cs, gates]");
@@ -232,10 +469,19 @@ void rnn_replica_step_(const std::string& cell, py::list xs, py::list ys, py::li
 void register_rnn(py::module& m) {
   m.def("rnn_fwd", &rnn_fwd_, "persistent GRU/LSTM/SimpleRNN forward (fp32)", py::arg("cell"), py::arg("x"),
         py::arg("W"), py::arg("U"), py::arg("b"), py::arg("rs"), py::arg("act") = (int64_t)ACT_C_TANH,
-        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID);
+        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID, py::arg("reverse") = false, py::arg("y_input_order") = false);
   m.def("rnn_bwd", &rnn_bwd_, "persistent GRU/LSTM backward (fp32)", py::arg("cell"), py::arg("dy"), py::arg("x"),
         py::arg("W"), py::arg("U"), py::arg("b"), py::arg("rs"), py::arg("saved"), py::arg("gW") = py::none(),
         py::arg("gU") = py::none(), py::arg("gb") = py::none(), py::arg("need_dx") = true,
+        py::arg("act") = (int64_t)ACT_C_TANH, py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID,
+        py::arg("reverse") = false, py::arg("y_input_order") = false);
+  m.def("birnn_fwd", &birnn_fwd_, "Bidirectional GRU/LSTM/SimpleRNN forward: both directions in one recurrence launch",
+        py::arg("cell"), py::arg("x"), py::arg("Ws"), py::arg("Us"), py::arg("bs"), py::arg("rs"),
+        py::arg("merge") = "concat", py::arg("act") = (int64_t)ACT_C_TANH,
+        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID);
+  m.def("birnn_bwd", &birnn_bwd_, "Bidirectional backward: one recurrence launch, parameter gradients per direction",
+        py::arg("cell"), py::arg("dy"), py::arg("x"), py::arg("Ws"), py::arg("Us"), py::arg("bs"), py::arg("rs"),
+        py::arg("merge"), py::arg("saved"), py::arg("gWs"), py::arg("gUs"), py::arg("gbs"), py::arg("need_dx") = true,
         py::arg("act") = (int64_t)ACT_C_TANH, py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID);
   m.def("rnn_replica_step", &rnn_replica_step_, "one training step of R co-located RNN -> Dense / MSE replicas");
   m.def("rnn_replica_ok", [](const std::string& cell, int64_t H, int64_t I, int64_t K, int64_t B) {

@@ -326,7 +326,7 @@ class _Recurrent(Layer):
     cell = "rnn"
 
     def __init__(self, units, activation="tanh", recurrent_activation="hard_sigmoid", return_sequences=False,
-                 use_bias=True, unit_forget_bias=True, **kw):
+                 use_bias=True, unit_forget_bias=True, go_backwards=False, **kw):
         super().__init__(**kw)
         self.units = int(units)
         self.activation = activation
@@ -334,6 +334,8 @@ class _Recurrent(Layer):
         self.return_sequences = return_sequences
         self.use_bias = use_bias
         self.unit_forget_bias = unit_forget_bias
+        # Keras: process the sequence last-to-first; a returned sequence is in processing order (reversed)
+        self.go_backwards = bool(go_backwards)
 
     def build(self, s):
         T, fin = s
@@ -367,12 +369,12 @@ class _Recurrent(Layer):
             self.cell, x, self.kernel.data, self.recurrent_kernel.data, None if self.bias is None else self.bias.data,
             grads=(self.kernel.grad, self.recurrent_kernel.grad, None if self.bias is None else self.bias.grad),
             return_sequences=self.return_sequences, activation=self.activation,
-            recurrent_activation=self.recurrent_activation, on_grad=self.grad_hook)
+            recurrent_activation=self.recurrent_activation, on_grad=self.grad_hook, go_backwards=self.go_backwards)
 
     def get_config(self):
         return {**super().get_config(), "units": self.units, "activation": self.activation,
                 "recurrent_activation": self.recurrent_activation, "return_sequences": self.return_sequences,
-                "use_bias": self.use_bias}
+                "use_bias": self.use_bias, "go_backwards": self.go_backwards}
 
 
 class GRU(_Recurrent):
@@ -393,3 +395,74 @@ class LSTM(_Recurrent):
 class SimpleRNN(_Recurrent):
     n_gates = 1
     cell = "rnn"
+
+
+class Bidirectional(Layer):
+    """Keras ``Bidirectional`` wrapper of a recurrent layer: a forward copy and a backward copy
+    (``go_backwards`` flipped) built from the wrapped layer's config; the backward sequence output is
+    re-reversed to input time order before the merge (``concat`` / ``sum`` / ``ave``).  Both directions
+    run as one op (``ops.rnn.bidirectional``): one recurrence launch per pass on the GPU.
+
+    Weights (Keras order): forward kernel, recurrent kernel, bias, then the backward layer's; parameter
+    names ``<wrapper>/forward_<layer>/...`` and ``<wrapper>/backward_<layer>/...``."""
+
+    def __init__(self, layer, merge_mode="concat", **kw):
+        if isinstance(layer, dict):  # a Keras config ({"class_name", "config"})
+            from .core import layer_from_config
+
+            layer = layer_from_config(layer)
+        if not isinstance(layer, _Recurrent):
+            raise ValueError("Bidirectional wraps a recurrent layer (GRU / LSTM / SimpleRNN)")
+        if merge_mode not in rnn_ops.MERGE_MODES:
+            raise ValueError(f"Bidirectional merge_mode {merge_mode!r} is not supported "
+                             f"(supported: {', '.join(rnn_ops.MERGE_MODES)})")
+        if "input_shape" not in kw and "batch_input_shape" not in kw and layer._input_shape_arg is not None:
+            kw["input_shape"] = layer._input_shape_arg
+        super().__init__(**kw)
+        self.layer = layer
+        self.merge_mode = merge_mode
+        cfg = layer.get_config()
+        cfg.pop("batch_input_shape", None)
+        self.forward_layer = type(layer).from_config({**cfg, "name": f"{self.name}/forward_{layer.name}"})
+        self.backward_layer = type(layer).from_config({**cfg, "name": f"{self.name}/backward_{layer.name}",
+                                                       "go_backwards": not layer.go_backwards})
+        self.forward_layer.trainable = self.backward_layer.trainable = self.trainable and layer.trainable
+
+    def sublayers(self):
+        return [self.forward_layer, self.backward_layer]
+
+    def build(self, s):
+        for l in self.sublayers():
+            l.ensure_built(s)
+
+    def compute_output_shape(self, s):
+        out = tuple(self.forward_layer.compute_output_shape(s))
+        return (*out[:-1], 2 * out[-1]) if self.merge_mode == "concat" else out
+
+    def _fire_hooks(self):
+        for l in (self.forward_layer, self.backward_layer, self):
+            if l.grad_hook is not None:
+                l.grad_hook()
+
+    def call(self, x, training=False):
+        f, b = self.forward_layer, self.backward_layer
+        if f.go_backwards:
+            # a wrapped go_backwards layer (rare): Keras then returns both sequences in reversed time order;
+            # composed from the two single-direction ops
+            yf, yb = f.call(x, training), b.call(x, training)
+            if f.return_sequences:
+                yb = yb.flip(1)
+            if self.merge_mode == "concat":
+                return torch.cat([yf, yb], -1)
+            return yf + yb if self.merge_mode == "sum" else (yf + yb) * 0.5
+        wts = lambda l: (l.kernel.data, l.recurrent_kernel.data, None if l.bias is None else l.bias.data)
+        grads = lambda l: (l.kernel.grad, l.recurrent_kernel.grad, None if l.bias is None else l.bias.grad)
+        y = rnn_ops.bidirectional(f.cell, x, wts(f), wts(b), grads=(grads(f), grads(b)), merge_mode=self.merge_mode,
+                                  return_sequences=f.return_sequences, activation=f.activation,
+                                  recurrent_activation=f.recurrent_activation, on_grad=self._fire_hooks)
+        return y
+
+    def get_config(self):
+        return {**super().get_config(), "layer": {"class_name": type(self.layer).__name__,
+                                                  "config": self.layer.get_config()},
+                "merge_mode": self.merge_mode}

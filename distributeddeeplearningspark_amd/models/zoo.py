@@ -4,6 +4,7 @@
                       1,048,853 params.
 * ``gru_regressor``   GRU(128, input (25,1)) + Dense(1) (``ddl_nyiso_aztk.py:201-203``), 50,049.
 * ``lstm_regressor``  LSTM(128) + Dense(1) (``ddl_nyiso_aztk.py:249-251``), 66,689.
+* ``bigru_regressor`` / ``bilstm_regressor``  the same regressors with a ``Bidirectional`` (concat) recurrent layer.
 * ``lenet5``          LeNet-5 on MNIST shape (BASELINE.json config #1).
 * ``vgg16``           VGG-16 (BN) in the CIFAR shape (BASELINE.json config #4).
 * ResNet-50 lives in ``resnet.py``; BERT-base in ``bert.py``.
@@ -11,7 +12,7 @@
 from __future__ import annotations
 
 from .core import Sequential
-from .layers import (GRU, LSTM, Activation, BatchNormalization, Conv2D, Dense, Dropout, Flatten,
+from .layers import (GRU, LSTM, Activation, BatchNormalization, Bidirectional, Conv2D, Dense, Dropout, Flatten,
                      MaxPooling2D)
 
 
@@ -40,6 +41,20 @@ def gru_regressor(units: int = 128, seq_len: int = 25, features: int = 1, output
 def lstm_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outputs: int = 1) -> Sequential:
     m = Sequential()
     m.add(LSTM(units, input_shape=(seq_len, features)))
+    m.add(Dense(outputs, activation="linear"))
+    return m
+
+
+def bigru_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outputs: int = 1) -> Sequential:
+    m = Sequential()
+    m.add(Bidirectional(GRU(units), input_shape=(seq_len, features)))
+    m.add(Dense(outputs, activation="linear"))
+    return m
+
+
+def bilstm_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outputs: int = 1) -> Sequential:
+    m = Sequential()
+    m.add(Bidirectional(LSTM(units), input_shape=(seq_len, features)))
     m.add(Dense(outputs, activation="linear"))
     return m
 

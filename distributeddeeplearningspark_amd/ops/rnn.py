@@ -12,6 +12,11 @@ register-resident kernel for narrow inputs); the recurrence runs in the persiste
 hard_sigmoid, H = 64/128), the generic kernels for every other activation pair, SimpleRNN and
 other widths.  CPU tensors use the reference path below.  Parameter gradients accumulate
 into the arena in one launch.
+
+``go_backwards`` (Keras: the sequence is processed last-to-first, a returned sequence is in
+processing order) and ``bidirectional`` (both directions as ONE autograd node: one recurrence
+launch per pass with the direction on ``blockIdx.y``, the concat output written in place) run
+the directed instantiations of the same kernels; nothing is flipped or concatenated in memory.
 """
 from __future__ import annotations
 
@@ -29,7 +34,10 @@ def _act(name):
     return lambda x: activation_ref(name, x)
 
 
-def recurrent_ref(cell, x, W, U, b, return_sequences, activation="tanh", recurrent_activation="hard_sigmoid"):
+def recurrent_ref(cell, x, W, U, b, return_sequences, activation="tanh", recurrent_activation="hard_sigmoid",
+                  go_backwards=False):
+    if go_backwards:  # Keras: reversed input; a returned sequence stays in processing order
+        x = x.flip(1)
     B, T, _ = x.shape
     H = U.shape[0]
     act, ract = _act(activation), _act(recurrent_activation)
@@ -62,22 +70,38 @@ def recurrent_ref(cell, x, W, U, b, return_sequences, activation="tanh", recurre
     return torch.stack(outs, 1) if return_sequences else h
 
 
+def bidirectional_ref(cell, x, fwd, bwd, return_sequences, merge_mode="concat", activation="tanh",
+                      recurrent_activation="hard_sigmoid"):
+    """Both directions through ``recurrent_ref``; the backward sequence is re-reversed before the merge."""
+    yf = recurrent_ref(cell, x, *fwd, return_sequences, activation, recurrent_activation)
+    yb = recurrent_ref(cell, x, *bwd, return_sequences, activation, recurrent_activation, go_backwards=True)
+    if return_sequences:
+        yb = yb.flip(1)
+    if merge_mode == "concat":
+        return torch.cat([yf, yb], -1)
+    return yf + yb if merge_mode == "sum" else (yf + yb) * 0.5
+
+
+def _act_codes(act, ract):
+    codes = C().ACT_CODES
+    for a in (act, ract):
+        if a not in codes or a == "gelu":
+            raise ValueError(f"recurrent activation {a!r} has no HIP kernel (supported: "
+                             f"{sorted(k for k in codes if k != 'gelu')})")
+    return codes[act], codes[ract]
+
+
 class _RecurrentFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, U, b, gW, gU, gb, cfg):
-        cell, rs, act, ract, hook = cfg
+        cell, rs, act, ract, hook, rev = cfg
         ctx.cfg = cfg
         dt = x.dtype
         xf, Wf, Uf = x.float(), W.float(), U.float()
         bf = None if b is None else b.float()
         if use_native(x):
-            codes = C().ACT_CODES
-            for a in (act, ract):
-                if a not in codes or a == "gelu":
-                    raise ValueError(f"recurrent activation {a!r} has no HIP kernel (supported: "
-                                     f"{sorted(k for k in codes if k != 'gelu')})")
-            ctx.codes = (codes[act], codes[ract])
-            y, saved = C().rnn_fwd(cell, xf.contiguous(), Wf.contiguous(), Uf.contiguous(), bf, rs, *ctx.codes)
+            ctx.codes = _act_codes(act, ract)
+            y, saved = C().rnn_fwd(cell, xf.contiguous(), Wf.contiguous(), Uf.contiguous(), bf, rs, *ctx.codes, rev)
             ctx.native = True
             ctx.grads = (gW, gU, gb)
             ctx.needs_dx = ctx.needs_input_grad[0]
@@ -85,14 +109,14 @@ class _RecurrentFn(torch.autograd.Function):
             return y.to(dt)
         ctx.native = False
         with torch.no_grad():
-            y = recurrent_ref(cell, xf, Wf, Uf, bf, rs, act, ract)
+            y = recurrent_ref(cell, xf, Wf, Uf, bf, rs, act, ract, rev)
         ctx.grads = (gW, gU, gb)
         ctx.save_for_backward(xf, Wf, Uf, bf)
         return y.to(dt)
 
     @staticmethod
     def backward(ctx, dy):
-        cell, rs, act, ract, hook = ctx.cfg
+        cell, rs, act, ract, hook, rev = ctx.cfg
         saved = ctx.saved_tensors
         xf, Wf, Uf, bf = saved[:4]
         gW, gU, gb = ctx.grads
@@ -100,9 +124,9 @@ class _RecurrentFn(torch.autograd.Function):
             # fast path: dW/dU/db are accumulated into the fp32 arena slices in-kernel (None here)
             fp32 = lambda t: t if t is not None and t.dtype == torch.float32 and t.is_contiguous() else None
             dx, dW, dU, db = C().rnn_bwd(cell, dy.float().contiguous(), xf, Wf, Uf, bf, rs, list(saved[4:]),
-                                         fp32(gW), fp32(gU), fp32(gb), ctx.needs_dx, *ctx.codes)
+                                         fp32(gW), fp32(gU), fp32(gb), ctx.needs_dx, *ctx.codes, rev)
         else:
-            fn = lambda xx, ww, uu, bb: recurrent_ref(cell, xx, ww, uu, bb, rs, act, ract)
+            fn = lambda xx, ww, uu, bb: recurrent_ref(cell, xx, ww, uu, bb, rs, act, ract, rev)
             dx, dW, dU, db = ref_grads(fn, [xf, Wf, Uf, bf], dy.float())
         accumulate(gW, dW)
         accumulate(gU, dU)
@@ -113,7 +137,82 @@ class _RecurrentFn(torch.autograd.Function):
 
 
 def recurrent(cell, x, W, U, b=None, *, grads=(None, None, None), return_sequences=False, activation="tanh",
-              recurrent_activation="hard_sigmoid", on_grad=None):
+              recurrent_activation="hard_sigmoid", on_grad=None, go_backwards=False):
     gW, gU, gb = grads
-    cfg = (cell, bool(return_sequences), activation, recurrent_activation, on_grad)
+    cfg = (cell, bool(return_sequences), activation, recurrent_activation, on_grad, bool(go_backwards))
     return _RecurrentFn.apply(x, W, U, b, gW, gU, gb, cfg)
+
+
+MERGE_MODES = ("concat", "sum", "ave")
+
+
+class _BidirectionalFn(torch.autograd.Function):
+    """(x, Wf, Uf, bf, Wb, Ub, bb) -> merged output of the forward and the backward direction."""
+
+    @staticmethod
+    def forward(ctx, x, Wf, Uf, bf, Wb, Ub, bb, grads, cfg):
+        cell, rs, act, ract, hook, merge = cfg
+        ctx.cfg, ctx.grads = cfg, grads
+        dt = x.dtype
+        xf = x.float()
+        ws = [None if t is None else t.float() for t in (Wf, Uf, bf, Wb, Ub, bb)]
+        if use_native(x):
+            ctx.codes = _act_codes(act, ract)
+            y, saved = C().birnn_fwd(cell, xf.contiguous(), [ws[0], ws[3]], [ws[1], ws[4]], [ws[2], ws[5]], rs, merge,
+                                     *ctx.codes)
+            ctx.native = True
+            ctx.needs_dx = ctx.needs_input_grad[0]
+            ctx.has_b = (bf is not None, bb is not None)
+            ctx.save_for_backward(xf, *(t for t in ws if t is not None), *saved)
+            return y.to(dt)
+        ctx.native = False
+        with torch.no_grad():
+            y = bidirectional_ref(cell, xf, ws[:3], ws[3:], rs, merge, act, ract)
+        ctx.has_b = (bf is not None, bb is not None)
+        ctx.save_for_backward(xf, *(t for t in ws if t is not None))
+        return y.to(dt)
+
+    @staticmethod
+    def backward(ctx, dy):
+        cell, rs, act, ract, hook, merge = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        xf = saved.pop(0)
+        ws = []
+        for has_b in ctx.has_b:
+            ws += [saved.pop(0), saved.pop(0), saved.pop(0) if has_b else None]
+        g = list(ctx.grads[0]) + list(ctx.grads[1])  # gWf, gUf, gbf, gWb, gUb, gbb
+        if ctx.native:
+            fp32 = lambda t: t if t is not None and t.dtype == torch.float32 and t.is_contiguous() else None
+            gg = [fp32(t) for t in g]
+            dx, pg = C().birnn_bwd(cell, dy.float().contiguous(), xf, [ws[0], ws[3]], [ws[1], ws[4]], [ws[2], ws[5]],
+                                   rs, merge, saved, [gg[0], gg[3]], [gg[1], gg[4]], [gg[2], gg[5]], ctx.needs_dx,
+                                   *ctx.codes)
+            d = list(pg[0]) + list(pg[1])
+        else:
+            live = [t for t in ws if t is not None]
+
+            def fn(xx, *flat):
+                it = iter(flat)
+                full = [None if t is None else next(it) for t in ws]
+                return bidirectional_ref(cell, xx, full[:3], full[3:], rs, merge, act, ract)
+
+            out = ref_grads(fn, [xf, *live], dy.float())
+            dx, it = out[0], iter(out[1:])
+            d = [None if t is None else next(it) for t in ws]
+        for buf, val in zip(g, d):
+            accumulate(buf, val)
+        if hook is not None:
+            hook()  # once: both directions' gradients are final here
+        return (None if dx is None else dx.to(dy.dtype)), None, None, None, None, None, None, None, None
+
+
+def bidirectional(cell, x, fwd, bwd, *, grads=((None, None, None), (None, None, None)), merge_mode="concat",
+                  return_sequences=False, activation="tanh", recurrent_activation="hard_sigmoid", on_grad=None):
+    """Bidirectional recurrent layer as one autograd node.  ``fwd`` / ``bwd`` = (W, U, b | None) of the forward and the
+    backward direction, ``grads`` their (gW, gU, gb) gradient buffers; the backward direction's sequence is
+    returned in input time order, merged by ``merge_mode`` (``concat`` / ``sum`` / ``ave``)."""
+    if merge_mode not in MERGE_MODES:
+        raise ValueError(f"merge_mode {merge_mode!r} is not supported (supported: {MERGE_MODES})")
+    (Wf, Uf, bf), (Wb, Ub, bb) = (tuple(fwd) + (None,))[:3], (tuple(bwd) + (None,))[:3]
+    cfg = (cell, bool(return_sequences), activation, recurrent_activation, on_grad, merge_mode)
+    return _BidirectionalFn.apply(x, Wf, Uf, bf, Wb, Ub, bb, tuple(tuple(t) for t in grads), cfg)

@@ -75,6 +75,8 @@ def why_not(group) -> str | None:
         if m.loss != "mean_squared_error" or m.arena.compute is not m.arena.master:
             return "loss is not MSE or compute is not fp32"
         rnn, dense = ls
+        if rnn.go_backwards:
+            return "go_backwards recurrent layer (the batched kernels run forward only)"
         if (rnn.return_sequences or not rnn.use_bias or rnn.activation != "tanh"
                 or rnn.recurrent_activation != "hard_sigmoid" or not rnn.trainable or not dense.trainable):
             return "recurrent layer outside the fused cell (return_sequences / no bias / activations / frozen)"
