@@ -59,7 +59,7 @@ void gemm(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int64_t
           c10::optional<at::Tensor> resid_mask, c10::optional<at::Tensor> bnr_x, c10::optional<at::Tensor> bnr_mask,
           c10::optional<at::Tensor> bnr_mean, int64_t rsub_h, int64_t rsub_w, c10::optional<at::Tensor> bnr_scale, c10::optional<at::Tensor> bnr_shift, int64_t split_stride,
           int64_t zcount, int64_t za, int64_t zb, int64_t zc, int64_t zbias, std::vector<int64_t> cls_tap0,
-          std::vector<int64_t> cls_nt, std::vector<int64_t> cls_coff) {
+          std::vector<int64_t> cls_nt, std::vector<int64_t> cls_coff, bool bnr_premask) {
   CHECK_CUDA(a);
   CHECK_CUDA(b);
   CHECK_CUDA(c);
@@ -212,8 +212,7 @@ void gemm(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int64_t
       p.bnr_mask = bnr_mask->data_ptr<uint8_t>();
     }
     if (bnr_scale || bnr_shift) {  // mode-2 mask (ReLU of the BN output recomputed from x)
-      TORCH_CHECK(bnr_scale && bnr_shift && !bnr_mask && (tile != kTileStream || !resid),
-                  "gemm: bnr scale/shift (no mask bits; no residual on the streaming kernel)");
+      TORCH_CHECK(bnr_scale && bnr_shift && !bnr_mask, "gemm: bnr scale/shift (no mask bits)");
       CHECK_F32(*bnr_scale);
       CHECK_F32(*bnr_shift);
       TORCH_CHECK(bnr_scale->numel() >= N && bnr_shift->numel() >= N && ((uintptr_t)bnr_scale->data_ptr() % 16) == 0 &&
@@ -222,6 +221,12 @@ void gemm(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int64_t
       p.bnr_scale = bnr_scale->data_ptr<float>();
       p.bnr_shift = bnr_shift->data_ptr<float>();
     }
+    if (bnr_premask) {  // masked store + sum only (GemmParams::bnr_premask)
+      TORCH_CHECK(bnr_mask.has_value() && !outmap.has_value(), "gemm: bnr_premask needs the mask bits and no output map");
+      p.bnr_premask = 1;
+    }
+  } else {
+    TORCH_CHECK(!bnr_premask, "gemm: bnr_premask without a BN-backward reduction");
   }
   (void)bm;
   if (tile == kTileConv3)
@@ -341,7 +346,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("bnr_scale") = py::none(), py::arg("bnr_shift") = py::none(),
         py::arg("split_stride") = 0, py::arg("zcount") = 1, py::arg("za") = 0, py::arg("zb") = 0, py::arg("zc") = 0,
         py::arg("zbias") = 0, py::arg("cls_tap0") = std::vector<int64_t>{}, py::arg("cls_nt") = std::vector<int64_t>{},
-        py::arg("cls_coff") = std::vector<int64_t>{});
+        py::arg("cls_coff") = std::vector<int64_t>{}, py::arg("bnr_premask") = false);
   m.def("conv3x3_wgrad", &conv3x3_wgrad, "3x3 stride-1 weight gradient (halo kernel): gw += dW", py::arg("dy"),
         py::arg("x"), py::arg("gw"), py::arg("ws"), py::arg("splits"), py::arg("tpb"), py::arg("pp") = false);
   m.def("conv3x3_wgrad_plan", &conv3x3_wgrad_plan_py,

@@ -107,6 +107,11 @@ struct GemmParams {
   const float* bnr_mean;    // [N] batch mean of bnr_x
   const float* bnr_scale;   // [N] BN scale / shift of the forward (mode-2 mask), or null
   const float* bnr_shift;
+  // bnr_premask (needs bnr_mask): the STORED output is the gradient under the mask bits (masked elements
+  // are written as zero) and only stats[shard][0][n] += sum_m d * relu is accumulated — bnr_x and bnr_mean
+  // are not read.  For a consumer that folds the BN backward through the 1x1 conv behind it (bn_fold.hip)
+  // and so needs neither the unmasked gradient nor the BN input.
+  int bnr_premask;
   // stride-2 residual: when rsub_h > 0 the output rows m = (n, i, j) form an [N][rsub_h][rsub_w] grid
   // and ``resid`` lives on its stride-2 subgrid ([N][(rsub_h+1)/2][(rsub_w+1)/2], row stride ldr):
   // rows with even (i, j) add resid row ((n * Hs + i/2) * Ws + j/2), the others add nothing — the

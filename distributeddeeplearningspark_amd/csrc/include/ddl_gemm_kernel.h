@@ -440,6 +440,7 @@ __device__ __forceinline__ void unpack4(const uint2 v, float (&f)[4]) {
 // accumulated like the forward statistics (16-lane shuffle, one atomic per column and shard).  Output rows
 // may scatter through the OutMap (a strided data-gradient's parity class): x, the mask and the store then
 // use the destination row.  Column-outer so that only one column group's mean / scale / shift is live.
+// bnr_premask: the masked gradient is what gets stored and only its column sums are formed (x, mean not read).
 template <int RM, int RN>
 __device__ __forceinline__ void gemm_epilogue_bnr(const GemmParams& p, f32x4 (&acc)[RM][RN], const int mb,
                                                   const int nb, const int lane, const int bid, const int mlim) {
@@ -547,7 +548,7 @@ __device__ __forceinline__ void gemm_epilogue_bnr(const GemmParams& p, f32x4 (&a
         const int n = nb + 16 * j + ncol;  // host check: N % 4 == 0, so n < N covers n .. n+3
         const bool nok = n < p.N;
         float mu[4] = {0.f, 0.f, 0.f, 0.f}, sc[4] = {0.f, 0.f, 0.f, 0.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
-        if (nok) {
+        if (nok && !p.bnr_premask) {
           const float4 a = *reinterpret_cast<const float4*>(p.bnr_mean + n);
           mu[0] = a.x; mu[1] = a.y; mu[2] = a.z; mu[3] = a.w;
           if (p.bnr_scale) {
@@ -562,7 +563,8 @@ __device__ __forceinline__ void gemm_epilogue_bnr(const GemmParams& p, f32x4 (&a
           const int m = mb + 16 * i + mrow;
           if (!nok || m >= mlim) continue;
           const long off = rowoff[i] + n;
-          const uint2 xv = *reinterpret_cast<const uint2*>(X + off);
+          // bnr_premask: x is not read (zeros: s2 stays 0) and the masked gradient is what gets stored
+          const uint2 xv = p.bnr_premask ? make_uint2(0u, 0u) : *reinterpret_cast<const uint2*>(X + off);
           uint32_t mbits = 0xfu;
           if (p.bnr_mask) mbits = (uint32_t)p.bnr_mask[off >> 3] >> (off & 7);
           float rv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -593,6 +595,7 @@ __device__ __forceinline__ void gemm_epilogue_bnr(const GemmParams& p, f32x4 (&a
             bool keep = (mbits >> e) & 1u;
             if (p.bnr_scale) keep = (x[e] * sc[e] + sh[e]) > 0.f;
             const float d = keep ? bf2f(o[e]) : 0.f;
+            if (p.bnr_premask && !keep) o[e] = 0;
             s1[j][e] += d;
             s2[j][e] += d * (x[e] - mu[e]);
           }

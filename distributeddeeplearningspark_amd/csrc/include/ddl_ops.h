@@ -51,6 +51,18 @@ int bn_bwd_dx(const void* dy, const void* x, const void* y, const float* scale, 
               const float* coef, void* dx, void* dres, long M, int C, int mode, hipStream_t s,
               const void* x2 = nullptr, const float* mean2 = nullptr, float* ws2 = nullptr);
 
+// BN backward folded through the 1x1 conv in front of it (bn_fold.hip): w [Co][ldw] bf16, P = g^T y2 [Co][Ci],
+// S = y2^T y2 [Ci][Ci], wsg the producer's [kBnShards][2][Co] sums of the masked gradient g, wsy the
+// [rows][2][Ci] partial rows of a bn_stats sweep over y2.
+//   bn_fold_sums: sums[2][Co] (bn_bwd_finalize's ws with S = 1: sum g, sum g (yc - mean)) and
+//                 s[Ci] += sum_p y2 (s zeroed by the caller)
+//   bn_fold_coef: from coef (A, B, K): WA = bf16(A (.) w) [Co][Ci], WAt its transpose, Gm [Ci][Ci] bf16,
+//                 kv [Ci], dW [Co][lddw] += A P + B (w S) + K (x) s.  Co % 128 == 0, Ci % 64 == 0.
+int bn_fold_sums(const void* w, long ldw, const float* P, const float* wsg, const float* mean, const float* wsy,
+                 int rows, float* sums, float* s, int Co, int Ci, hipStream_t st);
+int bn_fold_coef(const void* w, long ldw, const float* P, const float* S, const float* s, const float* coef, void* WA,
+                 void* WAt, void* Gm, float* kv, float* dW, long lddw, int Co, int Ci, hipStream_t st);
+
 // ResNet stem: BN backward through the fused 3x3 / 2 / pad-1 max pool (pooled gradient dy + argmax bytes, the
 // BN output gradient recomputed per pixel, never stored): dx == nullptr -> reduce partials into ws
 // [S][2][C] (one row per workgroup); else dx = A d' + B x + K (coef) — bn.hip

@@ -22,7 +22,6 @@ int launch_gemm_bf16(const GemmParams& p_in, int epi, int tile, void* stream) {
        (p.resid && (p.ldr % 4 || (uintptr_t)p.resid % 8)) || p.aux || p.drop_thresh || p.bias || p.relu || p.N % 4 || p.ldc % 8 ||
        !(p.a_mode == OP_KC || p.a_mode == OP_KC_GATHER) || (p.a_mode == OP_KC_GATHER && p.b_mode != OP_KC)))
     return (int)hipErrorInvalidValue;
-  if (p.bnr_scale && tile == kTileStream && p.resid) return (int)hipErrorInvalidValue;  // streaming: mode 2 w/o residual
   const bool plain = (p.a_mode == OP_KC || p.a_mode == OP_RC) && (p.b_mode == OP_KC || p.b_mode == OP_RC);
   if (tile == kTile256) {  // 256x256 ping-pong kernel: plain operands, K and k_split % 64
     if (!plain || p.K % 64 || p.k_split % 64 || p.om.enabled) return (int)hipErrorInvalidValue;

@@ -158,7 +158,9 @@ template <bool ASM> __device__ __forceinline__ unsigned sld8(const void* p) {
 
 
 // BNR: 0 off; 1 the ReLU mask of the BN-backward reduce from GemmParams::bnr_mask (bits, or all ones);
-// 2 recomputed from the BN input as x * bnr_scale + bnr_shift > 0 (a BN without residual: mode 2)
+// 2 recomputed from the BN input as x * bnr_scale + bnr_shift > 0 (a BN without residual: mode 2);
+// 3 (GemmParams::bnr_premask) the mask bits are applied to the STORED vector and only the sum of the masked
+// gradient is accumulated: neither bnr_x nor bnr_mean is read
 template <int WN, int K, int BMODE, bool RES, int BNR = 0>
 __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const GemmParams p) {
   using namespace gst;
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
   // BNR: batch mean of the 8 columns this thread reads out (loaded once)
   float bmu[8];
   float bsc[BNR == 2 ? 8 : 1], bsh[BNR == 2 ? 8 : 1];
-  if constexpr (BNR != 0) {
+  if constexpr (BNR == 1 || BNR == 2) {
     const float4 a = *reinterpret_cast<const float4*>(p.bnr_mean + n0 + oc * 8);
     const float4 b = *reinterpret_cast<const float4*>(p.bnr_mean + n0 + oc * 8 + 4);
     bmu[0] = a.x; bmu[1] = a.y; bmu[2] = a.z; bmu[3] = a.w;
@@ -274,16 +276,17 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
       }
     }
     // BNR: the BN input x and its ReLU-mask byte at this thread's read-out vectors
-    u32x4_t bx[BNR ? CF::S : 1];
-    unsigned bm8[BNR == 1 ? CF::S : 1];
+    u32x4_t bx[(BNR == 1 || BNR == 2) ? CF::S : 1];
+    unsigned bm8[(BNR == 1 || BNR == 3) ? CF::S : 1];
     if constexpr (BNR) {
 #pragma unroll
       for (int ps = 0; ps < CF::S; ++ps) {
         const int m = min(m0 + orow + ps * CF::RPP, p.M - 1);
         const long idx = (long)m * p.ldc + n0 + oc * 8;
-        bx[ps] = sld128<kAsmSide>(reinterpret_cast<const bf16_t*>(p.bnr_x) + idx);
+        if constexpr (BNR != 3) bx[ps] = sld128<kAsmSide>(reinterpret_cast<const bf16_t*>(p.bnr_x) + idx);
         if constexpr (BNR == 1)
           bm8[ps] = sld8<kAsmSide>(p.bnr_mask ? (const void*)(p.bnr_mask + (idx >> 3)) : (const void*)p.bnr_x);
+        if constexpr (BNR == 3) bm8[ps] = sld8<kAsmSide>(p.bnr_mask + (idx >> 3));
       }
     }
     const int ahead = i + CF::NBUF - 1;
@@ -311,7 +314,7 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
     // counted waits (asm side loads): the residual before the epilogue math, with the BN-reduce loads (issued
     // after it) and the refill DMA (the youngest) still in flight; the BN-reduce loads before the read-out.
     // The empty asm redefines each loaded register after its wait, so no use is scheduled above it.
-    constexpr int kBnrLoads = BNR == 1 ? 2 * CF::S : (BNR == 2 ? CF::S : 0);
+    constexpr int kBnrLoads = BNR == 1 ? 2 * CF::S : (BNR != 0 ? CF::S : 0);
     if constexpr (kAsmSide && RES) {
       wait_vm<CF::D + kBnrLoads>();
       __builtin_amdgcn_sched_barrier(0);
@@ -361,8 +364,8 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ps = 0; ps < CF::S; ++ps) {
-        asm volatile("" : "+v"(bx[ps]));
-        if constexpr (BNR == 1) asm volatile("" : "+v"(bm8[ps]));
+        if constexpr (BNR != 3) asm volatile("" : "+v"(bx[ps]));
+        if constexpr (BNR == 1 || BNR == 3) asm volatile("" : "+v"(bm8[ps]));
       }
     }
     // read-out: whole rows, 16 B per lane (each thread always owns the same 8 columns)
@@ -370,10 +373,24 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
     for (int ps = 0; ps < CF::S; ++ps) {
       const int r = orow + ps * CF::RPP;
       const int m = m0 + r;
-      const uint4 v = *reinterpret_cast<const uint4*>(stg + r * (CF::NB * 2) + ((oc ^ sw<CF::OCPR>(r)) << 4));
+      uint4 v = *reinterpret_cast<const uint4*>(stg + r * (CF::NB * 2) + ((oc ^ sw<CF::OCPR>(r)) << 4));
+      if constexpr (BNR == 3) {  // the mask byte's bit e keeps bf16 element e of the vector
+        const uint32_t b = bm8[ps];
+        v.x &= ((b & 1u) ? 0xffffu : 0u) | ((b & 2u) ? 0xffff0000u : 0u);
+        v.y &= ((b & 4u) ? 0xffffu : 0u) | ((b & 8u) ? 0xffff0000u : 0u);
+        v.z &= ((b & 16u) ? 0xffffu : 0u) | ((b & 32u) ? 0xffff0000u : 0u);
+        v.w &= ((b & 64u) ? 0xffffu : 0u) | ((b & 128u) ? 0xffff0000u : 0u);
+      }
       if (m < p.M) {
         *reinterpret_cast<uint4*>(Cout + (long)m * p.ldc + n0 + oc * 8) = v;
-        if constexpr (BNR) {  // BN-backward partial sums of the stored gradient (see GemmParams)
+        if constexpr (BNR == 3) {  // sum of the masked gradient only
+          const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            s1[2 * q] += __uint_as_float(wv[q] << 16);
+            s1[2 * q + 1] += __uint_as_float(wv[q] & 0xffff0000u);
+          }
+        } else if constexpr (BNR) {  // BN-backward partial sums of the stored gradient (see GemmParams)
           const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
           const uint32_t xv[4] = {bx[ps].x, bx[ps].y, bx[ps].z, bx[ps].w};
           uint32_t bmk = 0xffu;
@@ -464,10 +481,29 @@ int launch_ws(const GemmParams& p, hipStream_t s) {
   const int panels = p.N / CF::NB;
   const int mt = (p.M + gst::BM - 1) / gst::BM;
   const int gx = std::max(1, std::min(mt, 2 * num_cus() / std::max(1, panels)));
-  if (p.bnr_x && p.bnr_scale) {  // mode 2 (no residual: a BN + ReLU without a shortcut)
+  if (p.bnr_x && p.bnr_scale) {  // mode 2: a BN + ReLU without a shortcut
+    // with a residual only where a folded bn3 backward needs it (ops/fused_blocks.py): conv3's data-gradient
+    // of the 64-wide ResNet stage, [M, 256] x [256, 64] + r
+    constexpr bool kRes2 = WN == 16 && K == 256 && BMODE == OP_RC;
     if constexpr (kBnr) {
-      if (p.resid) return (int)hipErrorInvalidValue;
-      hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, false, 2>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+      if (p.resid) {
+        if constexpr (kRes2)
+          hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, true, 2>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+        else
+          return (int)hipErrorInvalidValue;
+      } else {
+        hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, false, 2>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+      }
+    } else {
+      return (int)hipErrorInvalidValue;
+    }
+  } else if (p.bnr_x && p.bnr_premask) {  // masked store + sum (the data-gradients are the row-contiguous form)
+    if constexpr (kBnr && kRes && BMODE == OP_RC) {
+      if (!p.bnr_mask) return (int)hipErrorInvalidValue;
+      if (p.resid)
+        hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, true, 3>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+      else
+        hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, false, 3>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
     } else {
       return (int)hipErrorInvalidValue;
     }
@@ -538,7 +574,7 @@ int launch_gemm_stream(const GemmParams& p, int epi, hipStream_t s) {
                   ((uintptr_t)p.a % 16 == 0) && ((uintptr_t)p.c % 16 == 0) &&
                   (p.b_mode == OP_RC || (uintptr_t)p.b % 16 == 0) && (!p.resid || (uintptr_t)p.resid % 8 == 0) &&
                   (!p.bnr_x || (p.stats && (uintptr_t)p.bnr_x % 16 == 0 && (uintptr_t)p.bnr_mean % 16 == 0)) &&
-                  (!p.bnr_scale || (p.bnr_shift && !p.resid && (uintptr_t)p.bnr_scale % 16 == 0 &&
+                  (!p.bnr_scale || (p.bnr_shift && (uintptr_t)p.bnr_scale % 16 == 0 &&
                                     (uintptr_t)p.bnr_shift % 16 == 0));
   if (!ok) return (int)hipErrorInvalidValue;
   return p.b_mode == OP_KC ? launch_panel<OP_KC>(p, nb, s) : launch_panel<OP_RC>(p, nb, s);

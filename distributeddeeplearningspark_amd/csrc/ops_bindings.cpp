@@ -125,6 +125,42 @@ void bn_bwd_finalize_(const at::Tensor& ws, int64_t M, int64_t C, c10::optional<
                          cur_stream()));
 }
 
+// BN backward folded through a 1x1 conv (bn_fold.hip).  w [Co, Ci] bf16 (unit column stride), P [Co, Ci] and
+// S [Ci, Ci] fp32, wsg [32, 2, Co], wsy [rows, 2, Ci]; outputs sums [2, Co], s [Ci].
+void bn_fold_sums_(const at::Tensor& w, const at::Tensor& P, const at::Tensor& wsg, const at::Tensor& mean,
+                   const at::Tensor& wsy, const at::Tensor& sums, const at::Tensor& s) {
+  GPU(w); F32(P); F32(wsg); F32(mean); F32(wsy); F32(sums); F32(s);
+  CK(w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "bn_fold_sums: w [Co, Ci] bf16");
+  const int64_t Co = w.size(0), Ci = w.size(1);
+  CK(P.numel() == Co * Ci && wsg.numel() == (int64_t)kBnShards * 2 * Co && mean.numel() >= Co && sums.numel() == 2 * Co &&
+         s.numel() == Ci && wsy.numel() % (2 * Ci) == 0 && wsy.numel() > 0,
+     "bn_fold_sums: shapes");
+  at::DeviceGuard g(w.device());
+  HIP_OK(bn_fold_sums(w.data_ptr(), w.stride(0), P.data_ptr<float>(), wsg.data_ptr<float>(), mean.data_ptr<float>(),
+                      wsy.data_ptr<float>(), (int)(wsy.numel() / (2 * Ci)), sums.data_ptr<float>(), s.data_ptr<float>(),
+                      (int)Co, (int)Ci, cur_stream()));
+}
+
+// coef [3 * Co] -> WA [Co, Ci], WAt [Ci, Co], Gm [Ci, Ci] (bf16), kv [Ci], dW [Co, Ci] (fp32, row stride free) +=
+void bn_fold_coef_(const at::Tensor& w, const at::Tensor& P, const at::Tensor& S, const at::Tensor& s,
+                   const at::Tensor& coef, const at::Tensor& WA, const at::Tensor& WAt, const at::Tensor& Gm,
+                   const at::Tensor& kv, const at::Tensor& dW) {
+  GPU(w); F32(P); F32(S); F32(s); F32(coef); BF16(WA); BF16(WAt); BF16(Gm); F32(kv);
+  CK(w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "bn_fold_coef: w [Co, Ci] bf16");
+  const int64_t Co = w.size(0), Ci = w.size(1);
+  CK(Co % 128 == 0 && Ci % 64 == 0, "bn_fold_coef: Co % 128, Ci % 64");
+  CK(P.numel() == Co * Ci && S.numel() == Ci * Ci && s.numel() == Ci && coef.numel() >= 3 * Co && WA.numel() == Co * Ci &&
+         WAt.numel() == Co * Ci && Gm.numel() == Ci * Ci && kv.numel() == Ci,
+     "bn_fold_coef: shapes");
+  CK(dW.is_cuda() && dW.scalar_type() == at::kFloat && dW.dim() == 2 && dW.size(0) == Co && dW.size(1) == Ci &&
+         dW.stride(1) == 1 && dW.stride(0) >= Ci,
+     "bn_fold_coef: dW [Co, Ci] fp32");
+  at::DeviceGuard g(w.device());
+  HIP_OK(bn_fold_coef(w.data_ptr(), w.stride(0), P.data_ptr<float>(), S.data_ptr<float>(), s.data_ptr<float>(),
+                      coef.data_ptr<float>(), WA.data_ptr(), WAt.data_ptr(), Gm.data_ptr(), kv.data_ptr<float>(),
+                      dW.data_ptr<float>(), dW.stride(0), (int)Co, (int)Ci, cur_stream()));
+}
+
 void bn_bwd_dx_(const at::Tensor& dy, const at::Tensor& x, c10::optional<at::Tensor> y,
                 c10::optional<at::Tensor> scale, c10::optional<at::Tensor> shift, const at::Tensor& coef,
                 const at::Tensor& dx, c10::optional<at::Tensor> dres, int64_t C, int64_t mode) {
@@ -709,6 +745,8 @@ void register_ops(py::module& m) {
         py::arg("res_shift") = py::none());
   m.def("bn_bwd_reduce", &bn_bwd_reduce_);
   m.def("bn_bwd_finalize", &bn_bwd_finalize_);
+  m.def("bn_fold_sums", &bn_fold_sums_);
+  m.def("bn_fold_coef", &bn_fold_coef_);
   m.def("bn_bwd_dx", &bn_bwd_dx_);
   m.def("bn_bwd_dx_red", &bn_bwd_dx_red_);
   m.def("pool3s2_bn_bwd", &pool3s2_bn_bwd_, py::arg("dy"), py::arg("am"), py::arg("x"), py::arg("scale"),

@@ -7,6 +7,12 @@ What the fusion buys over composing per-op autograd nodes:
   * every BN uses the statistics the producing conv's epilogue accumulated;
   * the BN backward ReLU masks are recomputed from the conv outputs (mode 2) except
     where a residual enters (mode 1), so no extra activation tensor is read;
+  * bn3's backward of an identity block folds through conv3 (``_FOLD_BN3``, default on; a module flag for
+    tests, not an environment knob): the next block's conv1 data-gradient stores the block-output gradient
+    under bn3's ReLU mask with its column sums, and conv3's weight / data gradients come from the small
+    products g^T y2, y2^T y2 (``fold_conv_bn_backward``, csrc/kernels/bn_fold.hip) — no dx sweep, no read of
+    conv3's output.  Only where it pays (``_FOLD_MIN_ELEMS``), never in deterministic mode, and only when the
+    gradient that arrives is the very tensor the producer wrote; otherwise the sweeps run as before;
   * all workspaces come from the per-step statistics pool;
   * parameter-gradient hooks (for the overlapped RCCL all-reduce) fire per layer in
     backward order as soon as each layer's gradients are final.
@@ -30,12 +36,17 @@ from .streams import on_grad_stream
 class _ConvBNState:
     """Per-(conv,BN) forward results needed by the backward.  ``pre_reduced``: the BN-backward
     partial sums [32, 2, C] already accumulated by the producer of this BN's output gradient
-    (the next block's conv1 data-gradient epilogue), so ``bn_backward`` skips its reduce sweep."""
+    (the next block's conv1 data-gradient epilogue), so ``bn_backward`` skips its reduce sweep.
+    ``pre_reduced = (ws, d, premasked)``; ``premasked``: ``d`` was stored under this BN's ReLU mask and ``ws``
+    holds only its column sums (what the folded bn3 backward needs, see ``_fold_bn3_backward``).
+    ``fold``: this is the bn3 of an identity bottleneck that may fold (set by the forward)."""
 
-    __slots__ = ("g", "yc", "y", "mean", "invstd", "scale", "shift", "mode", "mask", "pre_reduced", "__weakref__")
+    __slots__ = ("g", "yc", "y", "mean", "invstd", "scale", "shift", "mode", "mask", "pre_reduced", "fold",
+                 "__weakref__")
 
     def __init__(self):
         self.pre_reduced = None
+        self.fold = False
 
 
 # Block outputs -> the (ConvBN unit, state) of the BN that produced them (weak references only): the
@@ -125,7 +136,7 @@ def bn_backward(unit, st, dy, want_dres, red2=None, dy_mask=None, reduced=None):
     pre, st.pre_reduced = st.pre_reduced, None
     if reduced is not None:
         ws = reduced
-    elif pre is not None and _same_tensor(pre[1], dy):
+    elif pre is not None and not pre[2] and _same_tensor(pre[1], dy):
         # partial sums already accumulated by dy's producer (no reduce sweep) — valid only when dy IS the
         # gradient that producer reduced: a second consumer of this BN's output makes autograd sum the
         # gradients into a new tensor, and then the sweep runs on the sum
@@ -180,6 +191,7 @@ class _BottleneckFn(torch.autograd.Function):
         s2 = convbn_forward(block.c2, s1.y, relu=True)
         s3 = convbn_forward(block.c3, s2.y, resid=sc, relu=True,
                             res_affine=None if s_down is None else (s_down.scale, s_down.shift))
+        s3.fold = s_down is None and s3.mode == 3 and _fold_gate(s3.g)
         ctx.block, ctx.states = block, (s_down, s1, s2, s3)
         ctx.save_for_backward(x)
         ctx.needs_dx = ctx.needs_input_grad[0]
@@ -201,7 +213,17 @@ class _BottleneckFn(torch.autograd.Function):
         # gradient is never written, and the shortcut BN runs no reduce sweep
         fuse_down = _FUSE_DOWN and s_down is not None and s3.mode == 3 and s_down.mode == 0
         ws_d = None
-        if fuse_down:
+        # identity block whose output gradient arrived pre-masked with its column sums (the next block's conv1
+        # data-gradient, BNR premask): bn3's backward folds through conv3 — no dx sweep, no read of yc3
+        pre3 = s3.pre_reduced
+        fold = (_FOLD_BN3 and s3.fold and not _det.enabled() and pre3 is not None and pre3[2]
+                and _same_tensor(pre3[1], dout) and b.c3.bn.gamma is not None)
+        if fold:
+            s3.pre_reduced = None
+            bnr2 = _bnr_mode2(s2, dout.device)
+            d2 = _fold_bn3_backward(b.c3, s3, s2, dout, pre3[0], bnr2)
+            dsc = dout  # pre-masked: it is the shortcut's gradient as it stands
+        elif fuse_down:
             Cd = s_down.yc.shape[-1]
             ws_d = partials_workspace(s_down.yc.numel() // Cd, Cd, dout.device)
             d3c, dsc = bn_backward(b.c3, s3, dout, False, red2=(s_down.yc, s_down.mean, ws_d))
@@ -210,8 +232,9 @@ class _BottleneckFn(torch.autograd.Function):
         # the data-gradients of conv3 and conv2 produce bn2's / bn1's output gradients: their epilogues also
         # accumulate those BNs' backward partial sums (ReLU mask recomputed from yc), so bn_backward skips the
         # reduce sweep wherever the kernel that ran could take it (bnr["done"])
-        bnr2 = _bnr_mode2(s2, dout.device)
-        d2 = conv_backward(b.c3, s3, d3c, s2.y, True, bnr=bnr2)
+        if not fold:
+            bnr2 = _bnr_mode2(s2, dout.device)
+            d2 = conv_backward(b.c3, s3, d3c, s2.y, True, bnr=bnr2)
         _take_reduced(s2, bnr2, d2)
         d2c, _ = bn_backward(b.c2, s2, d2, False)
         bnr1 = _bnr_mode2(s1, dout.device)
@@ -243,7 +266,9 @@ class _BottleneckFn(torch.autograd.Function):
         if ctx.needs_dx and ctx.prev is not None and ctx.prev[1].mode == 3 and not _det.enabled():
             pst = ctx.prev[1]
             bnr = {"x": pst.yc, "mask": pst.mask, "mean": pst.mean,
-                   "ws": new_stats_workspace(pst.yc.shape[-1], dout.device)}
+                   "ws": new_stats_workspace(pst.yc.shape[-1], dout.device),
+                   # a folding identity block wants the masked gradient and its column sums only
+                   "premask": _FOLD_BN3 and pst.fold and s1.g.is_pointwise}
         if _TEST_MUTATION is not None and _TEST_MUTATION[0] == "drop_shortcut" and _TEST_MUTATION[1] in (None, b.name):
             # test-only fault (tests/test_gpu_determinism.py): the block's input gradient loses its shortcut term
             masked_sc, dsc, rsub = False, None, None
@@ -252,7 +277,7 @@ class _BottleneckFn(torch.autograd.Function):
         else:
             dx = conv_backward(b.c1, s1, d1c, x, ctx.needs_dx, resid=dsc, bnr=bnr, rsub=rsub)
         if bnr is not None and bnr.get("done"):
-            ctx.prev[1].pre_reduced = (bnr["ws"], dx)
+            ctx.prev[1].pre_reduced = (bnr["ws"], dx, bool(bnr["premask"]))
         ctx.states = ctx.prev = None
         return dx, None, None
 
@@ -281,7 +306,68 @@ def _bnr_mode2(st, device):
 
 def _take_reduced(st, bnr, d):
     if bnr is not None and bnr.get("done"):
-        st.pre_reduced = (bnr["ws"], d)
+        st.pre_reduced = (bnr["ws"], d, False)
+
+
+# bn3's backward of identity bottlenecks folded through conv3 (csrc/kernels/bn_fold.hip): monkeypatchable
+_FOLD_BN3 = True
+# it trades ~2.9 sweeps of the [M, Co] tensor for seven launch-sized kernels: folds where that tensor has at
+# least this many elements (measured per ResNet-50 stage at batch 256, docs/PERFORMANCE.md)
+_FOLD_MIN_ELEMS = 1 << 26
+
+
+def _fold_gate(g) -> bool:
+    return g.is_pointwise and g.Ci % 64 == 0 and g.Co % 128 == 0 and g.M * g.Co >= _FOLD_MIN_ELEMS
+
+
+def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbeta, bnr2=None, out=None):
+    """Backward of ``yc = y2 w^T -> BN`` (a 1x1 conv and the BN behind it) from the BN's output gradient ``g2``
+    [M, Co], already under the BN's ReLU mask, and its column sums ``ws_g`` ([32, 2, Co], row [:, 0]): with the
+    BN's dx = A g + B yc + K,
+        d2 = g (A.w) + y2 Gm + kv,  gw += A.P + B.(w S) + K x s,  P = g^T y2, S = y2^T y2, s = sum_p y2
+    (csrc/kernels/bn_fold.hip) — neither yc nor dx is read or written.  ``dgamma`` / ``dbeta`` accumulate as in
+    ``bn_bwd_finalize``; ``bnr2``: fused BN-backward reduce of d2 (``gemm.linear_dgrad``).
+    Returns (d2 [M, Ci] bf16, sums [2, Co]: sum g and sum g (yc - mean))."""
+    M, Co = g2.shape
+    Ci = y2.shape[1]
+    dev = g2.device
+    # P | S | s: zeroed fp32 accumulators (the two split-K products, the column sums), from the statistics pool
+    ps = new_stats_workspace(-(-(Co * Ci + Ci * Ci + Ci) // 64), dev).view(-1)
+    P, S = ps[: Co * Ci].view(Co, Ci), ps[Co * Ci : Co * Ci + Ci * Ci].view(Ci, Ci)
+    s = ps[Co * Ci + Ci * Ci : Co * Ci + Ci * Ci + Ci]
+    G.linear_wgrad(g2, y2, P)
+    G.linear_wgrad(y2, y2, S)
+    wsy = partials_workspace(M, Ci, dev)
+    C().bn_stats(y2, wsy, Ci)
+    f32 = torch.empty(5 * Co + Ci, dtype=torch.float32, device=dev)
+    sums, coef, kv = f32[: 2 * Co], f32[2 * Co : 5 * Co], f32[5 * Co :]
+    C().bn_fold_sums(w, P, ws_g, mean, wsy, sums, s)
+    C().bn_bwd_finalize(sums, M, Co, gamma, mean, invstd, dgamma, dbeta, coef)
+    b16 = torch.empty(2 * Co * Ci + Ci * Ci, dtype=torch.bfloat16, device=dev)
+    WA, WAt, Gm = b16[: Co * Ci].view(Co, Ci), b16[Co * Ci : 2 * Co * Ci].view(Ci, Co), b16[2 * Co * Ci :].view(Ci, Ci)
+    C().bn_fold_coef(w, P, S, s, coef, WA, WAt, Gm, kv, gw)
+    r = G.linear_fwd(y2, Gm, bias=kv)
+    if out is None:
+        out = torch.empty((M, Ci), dtype=torch.bfloat16, device=dev)
+    G.linear_dgrad(g2, WA, out=out, resid=r, bnr=bnr2, wt=WAt)
+    return out, sums.view(2, Co)
+
+
+def _fold_bn3_backward(unit, s3, s2, g, ws_g, bnr2):
+    """conv3 + bn3 backward of an identity bottleneck from the pre-masked output gradient ``g`` and its column
+    sums ``ws_g`` (``fold_conv_bn_backward``).  Returns d2."""
+    conv, bn = unit.conv, unit.bn
+    geo = s3.g
+    M, Co, Ci = geo.M, geo.Co, geo.Ci
+    d2 = torch.empty((geo.N, geo.H, geo.W, Ci), dtype=torch.bfloat16, device=g.device)
+    fold_conv_bn_backward(conv.kernel.data.view(Co, Ci), conv.kernel.grad.view(Co, Ci), g.view(M, Co), s2.y.view(M, Ci),
+                          ws_g, s3.mean, s3.invstd, bn.gamma.master, bn.gamma.grad,
+                          None if bn.beta is None else bn.beta.grad, bnr2=bnr2, out=d2.view(M, Ci))
+    if bn.grad_hook is not None:
+        bn.grad_hook()
+    if conv.grad_hook is not None:  # after the last read of the weights (see conv_backward)
+        conv.grad_hook()
+    return d2
 
 
 def _same_tensor(a, b) -> bool:

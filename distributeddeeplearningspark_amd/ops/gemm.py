@@ -164,7 +164,8 @@ def gemm(a, b, c, M, N, K, a_mode, b_mode, lda, ldb, ldc, epi, *, alpha=1.0, bet
              int(relu), geom, outmap, b_kdiv, b_tap_stride, stats, aux, float(drop_p), int(drop_seed), resid_mask,
              None if bnr is None else bnr["x"], None if bnr is None else bnr.get("mask"),
              None if bnr is None else bnr["mean"], *(rsub or (0, 0)), None if bnr is None else bnr.get("scale"),
-             None if bnr is None else bnr.get("shift"), split_stride)
+             None if bnr is None else bnr.get("shift"), split_stride,
+             bnr_premask=bool(bnr is not None and bnr.get("premask")))
     if split_stride:
         if defer_slabs:
             return out, math.ceil(K / k_split)
@@ -265,7 +266,8 @@ def splitk_workspace(M, N, device):
 _SPLITK_DGRAD = True
 
 
-def linear_dgrad(dy, w, out=None, resid=None, gelu_pre=None, stats=None, resid_mask=None, bnr=None, rsub=None):
+def linear_dgrad(dy, w, out=None, resid=None, gelu_pre=None, stats=None, resid_mask=None, bnr=None, rsub=None,
+                 wt=None):
     """dx[M,K] = dy[M,N] @ w[N,K] (* gelu'(gelu_pre)) (+resid) -> bf16 (w read row-contiguous).
 
     ``stats`` ([32, 2, K] fp32, zeroed): per-column sums / sums of squares of the output;
@@ -273,8 +275,11 @@ def linear_dgrad(dy, w, out=None, resid=None, gelu_pre=None, stats=None, resid_m
     residual is added; ``bnr`` = {"x", "mask", "mean", "ws"} (mode-3 bit mask) or {"x", "scale",
     "shift", "mean", "ws"} (mode 2: ReLU recomputed from x): the GEMM's epilogue also accumulates the
     BatchNorm-backward partial sums of the output (``GemmParams.bnr_*``) into ``ws`` and
-    ``bnr["done"]`` is set — the consumer BN then skips its reduce sweep.  Where no kernel can
-    (mode 2 with a residual on the streaming kernel, split-K) ``bnr`` is left untouched.  ``rsub = (H, W)``: the rows are an
+    ``bnr["done"]`` is set — the consumer BN then skips its reduce sweep.  ``bnr["premask"]`` (with
+    ``"mask"``): the output is stored under the mask and ``ws`` gets the sum of the masked gradient only
+    (``GemmParams.bnr_premask``).  Where no kernel can (mode 2 with a residual on the streaming kernel other
+    than the [M, 256] x [256, 64] one, split-K) ``bnr`` is left untouched.  ``wt``: ``w.t()`` contiguous,
+    when the caller has it already.  ``rsub = (H, W)``: the rows are an
     [N][H][W] grid and ``resid`` lives on its stride-2 subgrid (``GemmParams.rsub_h``)."""
     M, N = dy.shape
     K = w.shape[1]
@@ -310,14 +315,15 @@ def linear_dgrad(dy, w, out=None, resid=None, gelu_pre=None, stats=None, resid_m
                                          relu=act, resid=resid, ldr=ldr):
         # transpose the (small) weight once so the GEMM reads B K-contiguous with ds_read_b128 instead
         # of paired transposed LDS reads: the BERT-size data-gradients run ~1.4x faster this way
-        wt = transpose(w)
+        wt = transpose(w) if wt is None else wt
         fb = _bnr_plain_ok(bnr, stats, resid, gelu_pre, K)
         gemm(dy, wt, out, M, K, N, KC, KC, dy.stride(0), wt.stride(0), out.stride(0), EPI_BF16, resid=resid,
              ldr=ldr, relu=act, aux=gelu_pre, stats=stats, resid_mask=resid_mask, rsub=rsub, bnr=bnr if fb else None)
         if fb:
             bnr["done"] = True
         return out
-    if (bnr is not None and stats is None and ("scale" not in bnr or (resid is None and rsub is None))
+    if (bnr is not None and stats is None
+            and ("scale" not in bnr or (resid is None and rsub is None) or (rsub is None and (K, N) == (64, 256)))
             and use_stream(M, K, N, KC, RC, EPI_BF16, dy.stride(0), out.stride(0), aux=gelu_pre, relu=act,
                            resid=resid, ldr=ldr)):
         gemm(dy, w, out, M, K, N, KC, RC, dy.stride(0), w.stride(0), out.stride(0), EPI_BF16, resid=resid, ldr=ldr,
