@@ -59,7 +59,8 @@ void gemm(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int64_t
           c10::optional<at::Tensor> resid_mask, c10::optional<at::Tensor> bnr_x, c10::optional<at::Tensor> bnr_mask,
           c10::optional<at::Tensor> bnr_mean, int64_t rsub_h, int64_t rsub_w, c10::optional<at::Tensor> bnr_scale, c10::optional<at::Tensor> bnr_shift, int64_t split_stride,
           int64_t zcount, int64_t za, int64_t zb, int64_t zc, int64_t zbias, std::vector<int64_t> cls_tap0,
-          std::vector<int64_t> cls_nt, std::vector<int64_t> cls_coff, bool bnr_premask) {
+          std::vector<int64_t> cls_nt, std::vector<int64_t> cls_coff, bool bnr_premask,
+          c10::optional<at::Tensor> colscale, c10::optional<at::Tensor> relu_mask_out) {
   CHECK_CUDA(a);
   CHECK_CUDA(b);
   CHECK_CUDA(c);
@@ -225,8 +226,36 @@ void gemm(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int64_t
       TORCH_CHECK(bnr_mask.has_value() && !outmap.has_value(), "gemm: bnr_premask needs the mask bits and no output map");
       p.bnr_premask = 1;
     }
-  } else {
-    TORCH_CHECK(!bnr_premask, "gemm: bnr_premask without a BN-backward reduction");
+  } else if (bnr_premask) {  // masked store + sum without the BN input: neither x nor the mean is read
+    TORCH_CHECK(stats.has_value() && bnr_mask.has_value() && !bnr_scale && !bnr_shift && !outmap.has_value() &&
+                    epi == EPI_BF16 && tile != kTile256,
+                "gemm: bnr_premask needs a stats workspace, the mask bits, a bf16 epilogue and no output map");
+    TORCH_CHECK(tile == kTileStream || (tile != kTileConv3 && N % 4 == 0 && ldc % 8 == 0 && !bias && relu == 0 && !aux &&
+                                        drop_p == 0.0 && a_mode == OP_KC),
+                "gemm: bnr_premask outside the streaming kernel: plain data-gradient (a pointwise conv), N % 4 == 0, "
+                "ldc % 8 == 0, no bias / activation");
+    TORCH_CHECK(bnr_mask->is_cuda() && bnr_mask->scalar_type() == at::kByte && bnr_mask->is_contiguous() && ldc % 8 == 0 &&
+                    bnr_mask->numel() >= ((M - 1) * ldc + N + 7) / 8,
+                "gemm: bnr_mask must be uint8 [M * ldc / 8]");
+    p.bnr_mask = bnr_mask->data_ptr<uint8_t>();
+    p.bnr_premask = 1;
+  }
+  if (colscale || relu_mask_out) {  // a BN applied in the epilogue of the 1x1 conv in front of it (GemmParams::colscale)
+    TORCH_CHECK(tile == kTileStream && colscale.has_value() && resid.has_value() && b_mode == OP_KC && !stats && !bnr_x &&
+                    !bnr_premask && rsub_h == 0 && alpha == 1.0,
+                "gemm: colscale / relu_mask_out run on the streaming kernel's forward form with a residual, without "
+                "statistics or a BN-backward reduction; the column scale takes alpha's place (alpha == 1)");
+    CHECK_CUDA(*colscale);
+    CHECK_F32(*colscale);
+    TORCH_CHECK(colscale->is_contiguous() && colscale->numel() >= N && ((uintptr_t)colscale->data_ptr() % 16) == 0,
+                "gemm: colscale [N] fp32, 16-B aligned");
+    p.colscale = colscale->data_ptr<float>();
+    if (relu_mask_out) {
+      TORCH_CHECK(relu_mask_out->is_cuda() && relu_mask_out->scalar_type() == at::kByte && relu_mask_out->is_contiguous() &&
+                      relu_mask_out->numel() >= ((M - 1) * ldc + N + 7) / 8,
+                  "gemm: relu_mask_out must be uint8 [M * ldc / 8]");
+      p.relu_mask_out = relu_mask_out->data_ptr<uint8_t>();
+    }
   }
   (void)bm;
   if (tile == kTileConv3)
@@ -346,7 +375,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("bnr_scale") = py::none(), py::arg("bnr_shift") = py::none(),
         py::arg("split_stride") = 0, py::arg("zcount") = 1, py::arg("za") = 0, py::arg("zb") = 0, py::arg("zc") = 0,
         py::arg("zbias") = 0, py::arg("cls_tap0") = std::vector<int64_t>{}, py::arg("cls_nt") = std::vector<int64_t>{},
-        py::arg("cls_coff") = std::vector<int64_t>{}, py::arg("bnr_premask") = false);
+        py::arg("cls_coff") = std::vector<int64_t>{}, py::arg("bnr_premask") = false,
+        py::arg("colscale") = py::none(), py::arg("relu_mask_out") = py::none());
   m.def("conv3x3_wgrad", &conv3x3_wgrad, "3x3 stride-1 weight gradient (halo kernel): gw += dW", py::arg("dy"),
         py::arg("x"), py::arg("gw"), py::arg("ws"), py::arg("splits"), py::arg("tpb"), py::arg("pp") = false);
   m.def("conv3x3_wgrad_plan", &conv3x3_wgrad_plan_py,

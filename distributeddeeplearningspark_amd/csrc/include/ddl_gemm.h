@@ -139,6 +139,13 @@ struct GemmParams {
   int zcls;
   int cls_tap0[kMaxZCls], cls_nt[kMaxZCls];
   long cls_coff[kMaxZCls];
+  // a BatchNorm applied in the epilogue of the 1x1 conv in front of it (streaming kernel only, forward form with
+  // a residual): v = acc * colscale[n] + bias[n] (+ resid, ReLU) — the BN's scale in colscale (fp32 [N], replaces
+  // alpha), its shift in bias — and relu_mask_out (optional), the bn.hip mode-3 ReLU bit mask of the STORED
+  // output: byte (m*ldc + n) / 8, bit n % 8 set where stored bf16 element (m, n) is > 0.  (Last in the struct:
+  // the argument layout of every kernel that does not know them is unchanged.)
+  const float* colscale;
+  uint8_t* relu_mask_out;
 };
 
 enum Activation : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_GELU_BWD = 3 };

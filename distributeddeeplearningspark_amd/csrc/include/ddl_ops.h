@@ -62,6 +62,16 @@ int bn_fold_sums(const void* w, long ldw, const float* P, const float* wsg, cons
                  int rows, float* sums, float* s, int Co, int Ci, hipStream_t st);
 int bn_fold_coef(const void* w, long ldw, const float* P, const float* S, const float* s, const float* coef, void* WA,
                  void* WAt, void* Gm, float* kv, float* dW, long lddw, int Co, int Ci, hipStream_t st);
+// The forward side of the fold (conv3's output is never written; bn_fold.hip):
+//   gram_colsum:       S[Ci][Ci] += y2^T y2, s[Ci] += sum_p y2 in ONE read of y2 [M][ld] bf16 (S, s zeroed by the
+//                      caller; Ci in {64, 128, 256}, ld % 8 == 0; cus: compute units of the device)
+//   bn_fold_fwd_stats: bn3's batch sums from S and s: ws[0][0][co] = w_co . s, ws[0][1][co] = w_co^T S w_co
+//                      (evaluated around the mean, in double) into the zeroed [kBnShards][2][Co] workspace that
+//                      bn_finalize takes.  Ci % 32 == 0, Ci <= 256.
+//   bn_fold_sums with rows == 0 then leaves s alone (wsy unused).
+int gram_colsum(const void* y2, long ld, long M, int Ci, float* S, float* s, int cus, hipStream_t st);
+int bn_fold_fwd_stats(const void* w, long ldw, const float* S, const float* s, long M, float* ws, int Co, int Ci,
+                      hipStream_t st);
 
 // ResNet stem: BN backward through the fused 3x3 / 2 / pad-1 max pool (pooled gradient dy + argmax bytes, the
 // BN output gradient recomputed per pixel, never stored): dx == nullptr -> reduce partials into ws

@@ -17,7 +17,13 @@ int launch_gemm_bf16(const GemmParams& p_in, int epi, int tile, void* stream) {
   // ResNet-50 neutral; 128-tile GEMM 8192^3 810 -> 1089 TF/s (profiles/r3/ab/gemm_group_m.jsonl); 16 worse
   GemmParams p = p_in;
   p.group_m = 8;
-  if (p.bnr_x && tile != kTileStream &&  // fused BN-backward reduce on the other kernels: EPI_BF16_BNR
+  // the column-scale / ReLU-mask epilogue exists on the streaming kernel only
+  if ((p.colscale || p.relu_mask_out) && tile != kTileStream) return (int)hipErrorInvalidValue;
+  // premask reads neither bnr_x nor the mean: it is routed by the flag and needs the mask bits
+  if (p.bnr_premask && (!p.bnr_mask || !p.stats || p.bnr_scale)) return (int)hipErrorInvalidValue;
+  // ... without bnr_x only where a pointwise conv's data-gradient runs: the streaming and the plain-A kernels
+  if (p.bnr_premask && !p.bnr_x && tile != kTileStream && p.a_mode != OP_KC) return (int)hipErrorInvalidValue;
+  if ((p.bnr_x || p.bnr_premask) && tile != kTileStream &&  // fused BN-backward reduce on the other kernels: EPI_BF16_BNR
       (tile == kTile256 || epi != EPI_BF16 || p.om.zero_siblings ||
        (p.resid && (p.ldr % 4 || (uintptr_t)p.resid % 8)) || p.aux || p.drop_thresh || p.bias || p.relu || p.N % 4 || p.ldc % 8 ||
        !(p.a_mode == OP_KC || p.a_mode == OP_KC_GATHER) || (p.a_mode == OP_KC_GATHER && p.b_mode != OP_KC)))

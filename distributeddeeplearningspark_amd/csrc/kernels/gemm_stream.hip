@@ -30,7 +30,9 @@ constexpr int BM = 64;
 constexpr int LDS_BUDGET = 80 * 1024;
 typedef __attribute__((address_space(3))) void lds_t;
 
-template <int WN, int K>
+// CSM: the column-scale + ReLU-mask epilogue (gemm_stream_kernel): each 16-B read-out store is followed by the
+// one-byte store of its mask bits, so a tile's read-out issues 2 S VMEM stores per thread
+template <int WN, int K, bool CSM = false>
 struct Cfg {
   static constexpr int NB = 4 * WN;                 // panel width
   static constexpr int RN = WN / 16;                // 16-column MFMA blocks per wave
@@ -42,12 +44,13 @@ struct Cfg {
   static constexpr int STAGE = BM * NB * 2;         // staged output tile
   static constexpr int RPP = THREADS / OCPR;        // output rows per read-out pass
   static constexpr int S = BM / RPP;                // 16-B stores per thread per tile
+  static constexpr int SV = CSM ? 2 * S : S;        // VMEM stores per thread per tile (what vmcnt counts)
   static constexpr int NBUF_FIT = (LDS_BUDGET - STAGE) / TILE;
   static constexpr int NBUF = NBUF_FIT > 4 ? 4 : NBUF_FIT;
   static constexpr int LDS = NBUF * TILE + STAGE;
   static_assert(NBUF >= 2, "A ring needs two buffers");
   static_assert(D >= 1 && OCPR >= 8 && RPP >= 1 && BM % RPP == 0, "shape");
-  static_assert((NBUF - 1) * (D + S) <= 63, "vmcnt range");
+  static_assert((NBUF - 1) * (D + SV) <= 63, "vmcnt range");
   static_assert(4 * 2 * OCPR * 8 * 4 <= STAGE, "stats reduction fits in the staging buffer");
 };
 
@@ -67,14 +70,15 @@ __device__ __forceinline__ void wait_vm() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
 }
 
-template <class CF>
+// SV: VMEM stores per thread in each of those younger tiles' read-outs
+template <class CF, int SV = CF::S>
 __device__ __forceinline__ void wait_tile(int younger_store_tiles) {
   constexpr int base = (CF::NBUF - 1) * CF::D;
   switch (younger_store_tiles) {
     case 0: wait_vm<base>(); break;
-    case 1: wait_vm<base + CF::S>(); break;
-    case 2: wait_vm<base + 2 * CF::S>(); break;
-    default: wait_vm<base + 3 * CF::S>(); break;
+    case 1: wait_vm<base + SV>(); break;
+    case 2: wait_vm<base + 2 * SV>(); break;
+    default: wait_vm<base + 3 * SV>(); break;
   }
 }
 
@@ -161,10 +165,12 @@ template <bool ASM> __device__ __forceinline__ unsigned sld8(const void* p) {
 // 2 recomputed from the BN input as x * bnr_scale + bnr_shift > 0 (a BN without residual: mode 2);
 // 3 (GemmParams::bnr_premask) the mask bits are applied to the STORED vector and only the sum of the masked
 // gradient is accumulated: neither bnr_x nor bnr_mean is read
-template <int WN, int K, int BMODE, bool RES, int BNR = 0>
+// CSM (GemmParams::colscale / relu_mask_out): v = acc * colscale[n] + bias[n] instead of acc * alpha + bias[n],
+// and the read-out stores one byte of ReLU mask bits (taken from the stored bf16 values) per 16-B vector
+template <int WN, int K, int BMODE, bool RES, int BNR = 0, bool CSM = false>
 __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const GemmParams p) {
   using namespace gst;
-  using CF = Cfg<WN, K>;
+  using CF = Cfg<WN, K, CSM>;
   // side-operand loads as counted asm (see sld128) on every ring: on the two-slot K = 256 rings it keeps the
   // refill DMA in flight through the epilogue (ResNet-50 +0.9 %); on the deeper rings it measured equal to
   // compiler-tracked loads end to end (profiles/r6/stream_side_loads/)
@@ -208,6 +214,17 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
     bias_r[rn][1] = bv.y;
     bias_r[rn][2] = bv.z;
     bias_r[rn][3] = bv.w;
+  }
+  float csc_r[CSM ? CF::RN : 1][4];
+  if constexpr (CSM) {
+#pragma unroll
+    for (int rn = 0; rn < CF::RN; ++rn) {
+      const float4 cv = *reinterpret_cast<const float4*>(p.colscale + n0 + WN * w + 16 * rn + 4 * (lane >> 4));
+      csc_r[rn][0] = cv.x;
+      csc_r[rn][1] = cv.y;
+      csc_r[rn][2] = cv.z;
+      csc_r[rn][3] = cv.w;
+    }
   }
   wait_vm<0>();  // B fragments and bias in registers before the LDS-DMA ring starts
   auto tile_m0 = [&](int i) { return min((int)blockIdx.x + i * (int)gridDim.x, mt - 1) * BM; };
@@ -291,7 +308,12 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
     }
     const int ahead = i + CF::NBUF - 1;
     stage_a<CF>(A, p.lda, p.M, tile_m0(ahead), smem + (ahead % CF::NBUF) * CF::TILE, w, lane);
-    wait_tile<CF>(min(i, CF::NBUF - 1));
+    if constexpr (CSM) {  // without a mask output the read-outs issue S stores, not SV (block-uniform)
+      if (p.relu_mask_out) wait_tile<CF, CF::SV>(min(i, CF::NBUF - 1));
+      else wait_tile<CF>(min(i, CF::NBUF - 1));
+    } else {
+      wait_tile<CF>(min(i, CF::NBUF - 1));
+    }
     __builtin_amdgcn_s_barrier();  // tile i visible to every wave; previous read-out finished
 
     const char* abuf = smem + (i % CF::NBUF) * CF::TILE;
@@ -335,7 +357,10 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
         const int nl = WN * w + 16 * rn + 4 * (lane >> 4);
         float v[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[mb][rn][e], p.alpha, bias_r[rn][e]);
+        for (int e = 0; e < 4; ++e) {
+          if constexpr (CSM) v[e] = fmaf(acc[mb][rn][e], csc_r[rn][e], bias_r[rn][e]);
+          else v[e] = fmaf(acc[mb][rn][e], p.alpha, bias_r[rn][e]);
+        }
         if constexpr (RES) {
           const u32x2_t rv = rres[mb][rn];
           uint64_t mraw;
@@ -383,6 +408,18 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
       }
       if (m < p.M) {
         *reinterpret_cast<uint4*>(Cout + (long)m * p.ldc + n0 + oc * 8) = v;
+        if constexpr (CSM) {
+          if (p.relu_mask_out) {  // bit e: stored bf16 element e > 0 (positive, not NaN: bits in [1, 0x7f80])
+            const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+            uint32_t bits = 0u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              bits |= (((wv[q] & 0xffffu) - 1u) < 0x7f80u ? 1u : 0u) << (2 * q);
+              bits |= (((wv[q] >> 16) - 1u) < 0x7f80u ? 1u : 0u) << (2 * q + 1);
+            }
+            p.relu_mask_out[((long)m * p.ldc + n0 + oc * 8) >> 3] = (uint8_t)bits;
+          }
+        }
         if constexpr (BNR == 3) {  // sum of the masked gradient only
           const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -409,7 +446,7 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
               s2[e] += d * (xe - bmu[e]);
             }
           }
-        } else if (p.stats) {
+        } else if (!CSM && p.stats) {  // (the CSM launch takes no statistics: its accumulators are dead code)
           const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
@@ -425,7 +462,7 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
   }
   wait_vm<0>();  // no LDS-DMA may outlive the workgroup (the ring prefetches past the last tile)
 
-  if (p.stats) {
+  if (!CSM && p.stats) {
     // lanes of a wave with equal (lane % OCPR) own the same columns
 #pragma unroll
     for (int o = CF::OCPR; o < 64; o <<= 1)
@@ -481,7 +518,27 @@ int launch_ws(const GemmParams& p, hipStream_t s) {
   const int panels = p.N / CF::NB;
   const int mt = (p.M + gst::BM - 1) / gst::BM;
   const int gx = std::max(1, std::min(mt, 2 * num_cus() / std::max(1, panels)));
-  if (p.bnr_x && p.bnr_scale) {  // mode 2: a BN + ReLU without a shortcut
+  if (p.colscale || p.relu_mask_out) {
+    // a BN in the epilogue of the forward 1x1 conv in front of it, with the block's residual: the three ResNet
+    // conv3 shapes only (K = 64 on the 256-wide panel, K = 128 / 256 on the 128-wide one)
+    constexpr bool kCsm = BMODE == OP_KC && ((WN == 64 && K == 64) || (WN == 32 && K == 128) || (WN == 32 && K == 256));
+    if constexpr (kCsm) {
+      if (!p.colscale || !p.resid || p.bnr_x || p.bnr_premask || p.stats || p.rsub_h) return (int)hipErrorInvalidValue;
+      hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, true, 0, true>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+    } else {
+      return (int)hipErrorInvalidValue;
+    }
+  } else if (p.bnr_premask) {  // masked store + sum (the data-gradients are the row-contiguous form); no bnr_x
+    if constexpr (kBnr && kRes && BMODE == OP_RC) {
+      if (!p.bnr_mask || p.bnr_scale) return (int)hipErrorInvalidValue;
+      if (p.resid)
+        hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, true, 3>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+      else
+        hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, false, 3>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+    } else {
+      return (int)hipErrorInvalidValue;
+    }
+  } else if (p.bnr_x && p.bnr_scale) {  // mode 2: a BN + ReLU without a shortcut
     // with a residual only where a folded bn3 backward needs it (ops/fused_blocks.py): conv3's data-gradient
     // of the 64-wide ResNet stage, [M, 256] x [256, 64] + r
     constexpr bool kRes2 = WN == 16 && K == 256 && BMODE == OP_RC;
@@ -494,16 +551,6 @@ int launch_ws(const GemmParams& p, hipStream_t s) {
       } else {
         hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, false, 2>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
       }
-    } else {
-      return (int)hipErrorInvalidValue;
-    }
-  } else if (p.bnr_x && p.bnr_premask) {  // masked store + sum (the data-gradients are the row-contiguous form)
-    if constexpr (kBnr && kRes && BMODE == OP_RC) {
-      if (!p.bnr_mask) return (int)hipErrorInvalidValue;
-      if (p.resid)
-        hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, true, 3>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
-      else
-        hipLaunchKernelGGL((gemm_stream_kernel<WN, K, BMODE, false, 3>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
     } else {
       return (int)hipErrorInvalidValue;
     }
@@ -566,7 +613,7 @@ int launch_gemm_stream(const GemmParams& p, int epi, hipStream_t s) {
   if (p.resid && p.K == 128 && nb == 256) nb = 128;  // 256-wide panel + residual prefetch would spill
   // the fused BN-backward reduction prefetches x and the mask per read-out vector: narrower panels keep
   // those variants spill-free (128 wide up to K = 128, 64 at K = 256; A is re-read once more per panel)
-  if (p.bnr_x && nb > (p.K >= 256 ? 64 : 128)) nb = p.K >= 256 ? 64 : 128;
+  if ((p.bnr_x || p.bnr_premask) && nb > (p.K >= 256 ? 64 : 128)) nb = p.K >= 256 ? 64 : 128;
   const bool ok = nb && epi == EPI_BF16 && p.a_mode == OP_KC && (p.b_mode == OP_KC || p.b_mode == OP_RC) &&
                   !p.om.enabled && !p.aux && !p.drop_thresh && (p.relu == ACT_NONE || p.relu == ACT_RELU) &&
                   p.beta == 0.f && p.k_split >= p.K && p.lda % 8 == 0 && p.ldc % 8 == 0 &&
@@ -575,7 +622,9 @@ int launch_gemm_stream(const GemmParams& p, int epi, hipStream_t s) {
                   (p.b_mode == OP_RC || (uintptr_t)p.b % 16 == 0) && (!p.resid || (uintptr_t)p.resid % 8 == 0) &&
                   (!p.bnr_x || (p.stats && (uintptr_t)p.bnr_x % 16 == 0 && (uintptr_t)p.bnr_mean % 16 == 0)) &&
                   (!p.bnr_scale || (p.bnr_shift && (uintptr_t)p.bnr_scale % 16 == 0 &&
-                                    (uintptr_t)p.bnr_shift % 16 == 0));
+                                    (uintptr_t)p.bnr_shift % 16 == 0)) &&
+                  (!p.bnr_premask || (p.stats && p.bnr_mask)) &&
+                  (!p.colscale || (uintptr_t)p.colscale % 16 == 0);
   if (!ok) return (int)hipErrorInvalidValue;
   return p.b_mode == OP_KC ? launch_panel<OP_KC>(p, nb, s) : launch_panel<OP_RC>(p, nb, s);
 }

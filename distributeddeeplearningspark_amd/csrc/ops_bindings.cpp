@@ -127,18 +127,57 @@ void bn_bwd_finalize_(const at::Tensor& ws, int64_t M, int64_t C, c10::optional<
 
 // BN backward folded through a 1x1 conv (bn_fold.hip).  w [Co, Ci] bf16 (unit column stride), P [Co, Ci] and
 // S [Ci, Ci] fp32, wsg [32, 2, Co], wsy [rows, 2, Ci]; outputs sums [2, Co], s [Ci].
+// wsy None: s is complete already (gram_colsum) and is left alone.
 void bn_fold_sums_(const at::Tensor& w, const at::Tensor& P, const at::Tensor& wsg, const at::Tensor& mean,
-                   const at::Tensor& wsy, const at::Tensor& sums, const at::Tensor& s) {
-  GPU(w); F32(P); F32(wsg); F32(mean); F32(wsy); F32(sums); F32(s);
+                   c10::optional<at::Tensor> wsy, const at::Tensor& sums, const at::Tensor& s) {
+  GPU(w); F32(P); F32(wsg); F32(mean); F32(sums); F32(s);
   CK(w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "bn_fold_sums: w [Co, Ci] bf16");
   const int64_t Co = w.size(0), Ci = w.size(1);
   CK(P.numel() == Co * Ci && wsg.numel() == (int64_t)kBnShards * 2 * Co && mean.numel() >= Co && sums.numel() == 2 * Co &&
-         s.numel() == Ci && wsy.numel() % (2 * Ci) == 0 && wsy.numel() > 0,
+         s.numel() == Ci,
      "bn_fold_sums: shapes");
+  if (wsy) { F32(*wsy); CK(wsy->numel() % (2 * Ci) == 0 && wsy->numel() > 0, "bn_fold_sums: wsy [rows, 2, Ci]"); }
   at::DeviceGuard g(w.device());
   HIP_OK(bn_fold_sums(w.data_ptr(), w.stride(0), P.data_ptr<float>(), wsg.data_ptr<float>(), mean.data_ptr<float>(),
-                      wsy.data_ptr<float>(), (int)(wsy.numel() / (2 * Ci)), sums.data_ptr<float>(), s.data_ptr<float>(),
-                      (int)Co, (int)Ci, cur_stream()));
+                      optr<const float>(wsy), wsy ? (int)(wsy->numel() / (2 * Ci)) : 0, sums.data_ptr<float>(),
+                      s.data_ptr<float>(), (int)Co, (int)Ci, cur_stream()));
+}
+
+// S [Ci, Ci] += y2^T y2 and s [Ci] += column sums of y2 [M, Ci] bf16 (rows ld apart) in one read; S, s zeroed fp32.
+void gram_colsum_(const at::Tensor& y2, const at::Tensor& S, const at::Tensor& s) {
+  GPU(y2); GPU(S); GPU(s); F32(S); F32(s);
+  CK(y2.scalar_type() == at::kBFloat16 && y2.dim() == 2 && y2.stride(1) == 1 && y2.stride(0) % 8 == 0 &&
+         ((uintptr_t)y2.data_ptr() % 16) == 0,
+     "gram_colsum: y2 [M, Ci] bf16, 16-B aligned rows");
+  const int64_t M = y2.size(0), Ci = y2.size(1);
+  CK((Ci == 64 || Ci == 128 || Ci == 256) && M > 0 && y2.stride(0) >= Ci, "gram_colsum: Ci in {64, 128, 256}");
+  CK(S.numel() == Ci * Ci && s.numel() == Ci && ((uintptr_t)S.data_ptr() % 16) == 0, "gram_colsum: S [Ci, Ci], s [Ci]");
+  CK(S.device() == y2.device() && s.device() == y2.device(), "gram_colsum: y2, S and s on one device");
+  at::DeviceGuard g(y2.device());
+  // the grid is sized by the CU count of y2's device (looked up once per device)
+  static int cus_of[64] = {};
+  const int dev = y2.device().index();
+  int cus = dev >= 0 && dev < 64 ? cus_of[dev] : 0;
+  if (!cus) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (dev >= 0 && dev < 64) cus_of[dev] = cus;
+  }
+  HIP_OK(gram_colsum(y2.data_ptr(), y2.stride(0), M, (int)Ci, S.data_ptr<float>(), s.data_ptr<float>(), cus, cur_stream()));
+}
+
+// bn3's batch sums from S = y2^T y2 and s: ws [32, 2, Co] (zeroed) row 0 <- (w_co . s, w_co^T S w_co)
+void bn_fold_fwd_stats_(const at::Tensor& w, const at::Tensor& S, const at::Tensor& s, int64_t M, const at::Tensor& ws) {
+  GPU(w); GPU(S); GPU(s); GPU(ws); F32(S); F32(s); F32(ws);
+  CK(S.device() == w.device() && s.device() == w.device() && ws.device() == w.device(),
+     "bn_fold_fwd_stats: w, S, s and ws on one device");
+  CK(w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1, "bn_fold_fwd_stats: w [Co, Ci] bf16");
+  const int64_t Co = w.size(0), Ci = w.size(1);
+  CK(Ci % 32 == 0 && Ci <= 256 && M > 0 && S.numel() == Ci * Ci && s.numel() == Ci && ws.numel() >= 2 * Co &&
+         ((uintptr_t)S.data_ptr() % 16) == 0,
+     "bn_fold_fwd_stats: Ci % 32 == 0, Ci <= 256, S [Ci, Ci], s [Ci], ws [>= 1, 2, Co]");
+  at::DeviceGuard g(w.device());
+  HIP_OK(bn_fold_fwd_stats(w.data_ptr(), w.stride(0), S.data_ptr<float>(), s.data_ptr<float>(), M, ws.data_ptr<float>(),
+                           (int)Co, (int)Ci, cur_stream()));
 }
 
 // coef [3 * Co] -> WA [Co, Ci], WAt [Ci, Co], Gm [Ci, Ci] (bf16), kv [Ci], dW [Co, Ci] (fp32, row stride free) +=
@@ -747,6 +786,8 @@ void register_ops(py::module& m) {
   m.def("bn_bwd_finalize", &bn_bwd_finalize_);
   m.def("bn_fold_sums", &bn_fold_sums_);
   m.def("bn_fold_coef", &bn_fold_coef_);
+  m.def("gram_colsum", &gram_colsum_);
+  m.def("bn_fold_fwd_stats", &bn_fold_fwd_stats_);
   m.def("bn_bwd_dx", &bn_bwd_dx_);
   m.def("bn_bwd_dx_red", &bn_bwd_dx_red_);
   m.def("pool3s2_bn_bwd", &pool3s2_bn_bwd_, py::arg("dy"), py::arg("am"), py::arg("x"), py::arg("scale"),

@@ -13,6 +13,11 @@ What the fusion buys over composing per-op autograd nodes:
     products g^T y2, y2^T y2 (``fold_conv_bn_backward``, csrc/kernels/bn_fold.hip) — no dx sweep, no read of
     conv3's output.  Only where it pays (``_FOLD_MIN_ELEMS``), never in deterministic mode, and only when the
     gradient that arrives is the very tensor the producer wrote; otherwise the sweeps run as before;
+  * the forward of such a block never writes conv3's output either (``_FOLD_BN3_FWD``): bn3's batch statistics
+    follow from S = y2^T y2 and s = sum y2 (one read of the 4x narrower y2, ``gram_colsum``; the folded backward
+    needs both anyway), and conv3 applies bn3, the shortcut and the ReLU in its own epilogue, writing the block
+    output and the ReLU bit mask (``_convbn3_fold_forward``).  A backward that cannot fold recomputes conv3's
+    output first (``_recompute_yc``);
   * all workspaces come from the per-step statistics pool;
   * parameter-gradient hooks (for the overlapped RCCL all-reduce) fire per layer in
     backward order as soon as each layer's gradients are final.
@@ -29,7 +34,7 @@ from . import determinism as _det
 from . import gemm as G
 from . import zpad as ZP
 from ._native import C
-from .norm import new_stats_workspace, partials_workspace
+from .norm import new_stats_workspace, partials_workspace, pool_epoch
 from .streams import on_grad_stream
 
 
@@ -39,14 +44,16 @@ class _ConvBNState:
     (the next block's conv1 data-gradient epilogue), so ``bn_backward`` skips its reduce sweep.
     ``pre_reduced = (ws, d, premasked)``; ``premasked``: ``d`` was stored under this BN's ReLU mask and ``ws``
     holds only its column sums (what the folded bn3 backward needs, see ``_fold_bn3_backward``).
-    ``fold``: this is the bn3 of an identity bottleneck that may fold (set by the forward)."""
+    ``fold``: this is the bn3 of an identity bottleneck that may fold (set by the forward).
+    ``gram``: (S, s, statistics-pool epoch) of a forward that folded bn3 into conv3's epilogue — ``yc`` is None then."""
 
-    __slots__ = ("g", "yc", "y", "mean", "invstd", "scale", "shift", "mode", "mask", "pre_reduced", "fold",
+    __slots__ = ("g", "yc", "y", "mean", "invstd", "scale", "shift", "mode", "mask", "pre_reduced", "fold", "gram",
                  "__weakref__")
 
     def __init__(self):
         self.pre_reduced = None
         self.fold = False
+        self.gram = None
 
 
 # Block outputs -> the (ConvBN unit, state) of the BN that produced them (weak references only): the
@@ -189,8 +196,12 @@ class _BottleneckFn(torch.autograd.Function):
         sc = s_down.yc if s_down is not None else x
         s1 = convbn_forward(block.c1, x, relu=True)
         s2 = convbn_forward(block.c2, s1.y, relu=True)
-        s3 = convbn_forward(block.c3, s2.y, resid=sc, relu=True,
-                            res_affine=None if s_down is None else (s_down.scale, s_down.shift))
+        g3 = _fold_fwd_geometry(block.c3, s2.y) if s_down is None else None
+        if g3 is not None:
+            s3 = _convbn3_fold_forward(block.c3, s2.y, sc, g3)
+        else:
+            s3 = convbn_forward(block.c3, s2.y, resid=sc, relu=True,
+                                res_affine=None if s_down is None else (s_down.scale, s_down.shift))
         s3.fold = s_down is None and s3.mode == 3 and _fold_gate(s3.g)
         ctx.block, ctx.states = block, (s_down, s1, s2, s3)
         ctx.save_for_backward(x)
@@ -223,6 +234,11 @@ class _BottleneckFn(torch.autograd.Function):
             bnr2 = _bnr_mode2(s2, dout.device)
             d2 = _fold_bn3_backward(b.c3, s3, s2, dout, pre3[0], bnr2)
             dsc = dout  # pre-masked: it is the shortcut's gradient as it stands
+        elif s3.yc is None:
+            # the forward never wrote conv3's output and this backward does not fold (a second consumer, a
+            # producer that did not pre-mask, the network's last block): recompute it, then the sweeps as before
+            _recompute_yc(b.c3, s3, s2)
+            d3c, dsc = bn_backward(b.c3, s3, dout, want_dres=not masked_sc)
         elif fuse_down:
             Cd = s_down.yc.shape[-1]
             ws_d = partials_workspace(s_down.yc.numel() // Cd, Cd, dout.device)
@@ -265,10 +281,12 @@ class _BottleneckFn(torch.autograd.Function):
         bnr = None
         if ctx.needs_dx and ctx.prev is not None and ctx.prev[1].mode == 3 and not _det.enabled():
             pst = ctx.prev[1]
-            bnr = {"x": pst.yc, "mask": pst.mask, "mean": pst.mean,
-                   "ws": new_stats_workspace(pst.yc.shape[-1], dout.device),
-                   # a folding identity block wants the masked gradient and its column sums only
-                   "premask": _FOLD_BN3 and pst.fold and s1.g.is_pointwise}
+            # a folding identity block wants the masked gradient and its column sums only (neither x nor the mean
+            # is read: after a folded forward there is no x); without premask the reduce needs x = conv3's output
+            premask = bool(_FOLD_BN3 and pst.fold and s1.g.is_pointwise)
+            if premask or pst.yc is not None:
+                bnr = {"x": pst.yc, "mask": pst.mask, "mean": pst.mean,
+                       "ws": new_stats_workspace(pst.g.Co, dout.device), "premask": premask}
         if _TEST_MUTATION is not None and _TEST_MUTATION[0] == "drop_shortcut" and _TEST_MUTATION[1] in (None, b.name):
             # test-only fault (tests/test_gpu_determinism.py): the block's input gradient loses its shortcut term
             masked_sc, dsc, rsub = False, None, None
@@ -320,25 +338,98 @@ def _fold_gate(g) -> bool:
     return g.is_pointwise and g.Ci % 64 == 0 and g.Co % 128 == 0 and g.M * g.Co >= _FOLD_MIN_ELEMS
 
 
-def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbeta, bnr2=None, out=None):
+# the forward of a folding block: bn3 in conv3's epilogue, conv3's output never written.  Only effective with
+# _FOLD_BN3 (which restores the unfolded step when off); monkeypatchable
+_FOLD_BN3_FWD = True
+
+
+def _fold_fwd_geometry(unit, x2):
+    """conv3's geometry when this identity block's forward folds bn3 into conv3's epilogue, else None: the flags,
+    not in deterministic mode, a bn3 with a scale (as the backward's fold asks), the backward's gate, and a shape the streaming kernel's column-scale epilogue has."""
+    if not (_FOLD_BN3 and _FOLD_BN3_FWD) or _det.enabled() or x2.device.type != "cuda":
+        return None
+    if unit.bn.gamma is None:  # the backward never folds without a scale: every step would recompute conv3's output
+        return None
+    conv = unit.conv
+    N, H, W, Ci = x2.shape
+    kh, kw = conv.kernel_size
+    if (kh, kw) != (1, 1):
+        return None
+    p = conv.padding if isinstance(conv.padding, tuple) else (0, 0)
+    g = CV.geometry(N, H, W, Ci, conv.filters, kh, kw, conv.strides, p, conv.dilation_rate)
+    if not (_fold_gate(g) and G.stream_colscale_ok(g.Co, g.Ci) and x2.is_contiguous()):
+        return None
+    return g
+
+
+def _convbn3_fold_forward(unit, x2, resid, g):
+    """conv3 + bn3 + identity shortcut + ReLU of a folding block without conv3's output: S = x2^T x2 and
+    s = sum x2 (``gram_colsum``) -> bn3's batch sums (``bn_fold_fwd_stats``) -> ``bn_finalize`` as ever -> ONE
+    GEMM that applies scale / shift / shortcut / ReLU in its epilogue and writes y and the ReLU bit mask."""
+    conv, bn = unit.conv, unit.bn
+    M, Co, Ci = g.M, g.Co, g.Ci
+    dev = x2.device
+    x2m = x2.view(M, Ci)
+    # S | s: zeroed fp32 from the per-step statistics pool, which hands no memory out twice within a step, so
+    # they live until this step's backward (the epoch tells a backward that runs after a later reset)
+    ps = new_stats_workspace(-(-(Ci * Ci + Ci) // 64), dev).view(-1)
+    S, s = ps[: Ci * Ci].view(Ci, Ci), ps[Ci * Ci : Ci * Ci + Ci]
+    C().gram_colsum(x2m, S, s)
+    stats = new_stats_workspace(Co, dev)
+    w = conv.kernel.data.view(Co, Ci)
+    C().bn_fold_fwd_stats(w, S, s, M, stats)
+    gamma = None if bn.gamma is None else bn.gamma.master
+    beta = None if bn.beta is None else bn.beta.master
+    rm, rv = bn._states["moving_mean"], bn._states["moving_variance"]
+    scale, shift, mean, invstd = torch.empty(4, Co, dtype=torch.float32, device=dev).unbind(0)
+    C().bn_finalize(stats, M, Co, gamma, beta, bn.epsilon, 1.0 - bn.momentum, rm, rv, mean, invstd, scale, shift)
+    st = _ConvBNState()
+    st.g, st.yc = g, None
+    st.mask = torch.empty(-(-M * Co // 32) * 4, dtype=torch.uint8, device=dev)
+    y = torch.empty((g.N, g.H, g.W, Co), dtype=torch.bfloat16, device=dev)
+    G.linear_fwd(x2m, w, bias=shift, relu=True, out=y.view(M, Co), resid=resid.view(M, Co), colscale=scale,
+                 relu_mask_out=st.mask)
+    st.y, st.mean, st.invstd, st.scale, st.shift, st.mode = y, mean, invstd, scale, shift, 3
+    st.gram = (S, s, pool_epoch(dev))
+    return st
+
+
+def _recompute_yc(unit, s3, s2):
+    """conv3's output of a block whose forward did not write it (plain forward GEMM), for the unfolded sweeps."""
+    geo = s3.g
+    w = unit.conv.kernel.data.view(geo.Co, geo.Ci)
+    yc = torch.empty((geo.N, geo.H, geo.W, geo.Co), dtype=torch.bfloat16, device=s2.y.device)
+    G.linear_fwd(s2.y.view(geo.M, geo.Ci), w, out=yc.view(geo.M, geo.Co))
+    s3.yc = yc
+
+
+def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbeta, bnr2=None, out=None, gram=None):
     """Backward of ``yc = y2 w^T -> BN`` (a 1x1 conv and the BN behind it) from the BN's output gradient ``g2``
     [M, Co], already under the BN's ReLU mask, and its column sums ``ws_g`` ([32, 2, Co], row [:, 0]): with the
     BN's dx = A g + B yc + K,
         d2 = g (A.w) + y2 Gm + kv,  gw += A.P + B.(w S) + K x s,  P = g^T y2, S = y2^T y2, s = sum_p y2
     (csrc/kernels/bn_fold.hip) — neither yc nor dx is read or written.  ``dgamma`` / ``dbeta`` accumulate as in
     ``bn_bwd_finalize``; ``bnr2``: fused BN-backward reduce of d2 (``gemm.linear_dgrad``).
+    ``gram = (S, s)``: the forward formed them already (``gram_colsum``): neither the S product nor the
+    ``bn_stats`` sweep over y2 is launched.
     Returns (d2 [M, Ci] bf16, sums [2, Co]: sum g and sum g (yc - mean))."""
     M, Co = g2.shape
     Ci = y2.shape[1]
     dev = g2.device
     # P | S | s: zeroed fp32 accumulators (the two split-K products, the column sums), from the statistics pool
-    ps = new_stats_workspace(-(-(Co * Ci + Ci * Ci + Ci) // 64), dev).view(-1)
-    P, S = ps[: Co * Ci].view(Co, Ci), ps[Co * Ci : Co * Ci + Ci * Ci].view(Ci, Ci)
-    s = ps[Co * Ci + Ci * Ci : Co * Ci + Ci * Ci + Ci]
-    G.linear_wgrad(g2, y2, P)
-    G.linear_wgrad(y2, y2, S)
-    wsy = partials_workspace(M, Ci, dev)
-    C().bn_stats(y2, wsy, Ci)
+    if gram is not None:
+        S, s = gram
+        P = new_stats_workspace(-(-(Co * Ci) // 64), dev).view(-1)[: Co * Ci].view(Co, Ci)
+        G.linear_wgrad(g2, y2, P)
+        wsy = None
+    else:
+        ps = new_stats_workspace(-(-(Co * Ci + Ci * Ci + Ci) // 64), dev).view(-1)
+        P, S = ps[: Co * Ci].view(Co, Ci), ps[Co * Ci : Co * Ci + Ci * Ci].view(Ci, Ci)
+        s = ps[Co * Ci + Ci * Ci : Co * Ci + Ci * Ci + Ci]
+        G.linear_wgrad(g2, y2, P)
+        G.linear_wgrad(y2, y2, S)
+        wsy = partials_workspace(M, Ci, dev)
+        C().bn_stats(y2, wsy, Ci)
     f32 = torch.empty(5 * Co + Ci, dtype=torch.float32, device=dev)
     sums, coef, kv = f32[: 2 * Co], f32[2 * Co : 5 * Co], f32[5 * Co :]
     C().bn_fold_sums(w, P, ws_g, mean, wsy, sums, s)
@@ -360,9 +451,12 @@ def _fold_bn3_backward(unit, s3, s2, g, ws_g, bnr2):
     geo = s3.g
     M, Co, Ci = geo.M, geo.Co, geo.Ci
     d2 = torch.empty((geo.N, geo.H, geo.W, Ci), dtype=torch.bfloat16, device=g.device)
+    gram = None
+    if s3.gram is not None and s3.gram[2] == pool_epoch(g.device):  # the pool has not been reset since the forward
+        gram = s3.gram[:2]
     fold_conv_bn_backward(conv.kernel.data.view(Co, Ci), conv.kernel.grad.view(Co, Ci), g.view(M, Co), s2.y.view(M, Ci),
                           ws_g, s3.mean, s3.invstd, bn.gamma.master, bn.gamma.grad,
-                          None if bn.beta is None else bn.beta.grad, bnr2=bnr2, out=d2.view(M, Ci))
+                          None if bn.beta is None else bn.beta.grad, bnr2=bnr2, out=d2.view(M, Ci), gram=gram)
     if bn.grad_hook is not None:
         bn.grad_hook()
     if conv.grad_hook is not None:  # after the last read of the weights (see conv_backward)

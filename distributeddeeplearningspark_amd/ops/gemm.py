@@ -59,6 +59,15 @@ def stream_panel(N: int, K: int) -> int:
     return 0
 
 
+def stream_colscale_ok(N: int, K: int) -> bool:
+    """The streaming kernel has the column-scale / ReLU-mask epilogue (``linear_fwd(colscale=, relu_mask_out=)``)
+    for this forward shape with a residual: K = 64 on the 256-wide panel, K = 128 / 256 on the 128-wide one."""
+    nb = stream_panel(N, K)
+    if K == 128 and nb == 256:
+        nb = 128  # a residual forces the 128-wide panel there
+    return (nb, K) in ((256, 64), (128, 128), (128, 256))
+
+
 def use_stream(M, N, K, a_mode, b_mode, epi, lda, ldc, *, outmap=None, aux=None, drop_p=0.0, relu=0, beta=0.0,
                resid=None, ldr=0) -> bool:
     """Skinny-K streaming kernel: ResNet 1x1 convolutions and their data-gradients at large M
@@ -113,7 +122,7 @@ def choose_split(M: int, N: int, K: int, tile: int, allow: bool, rounds: float |
 def gemm(a, b, c, M, N, K, a_mode, b_mode, lda, ldb, ldc, epi, *, alpha=1.0, beta=0.0, bias=None, resid=None,
          ldr=0, relu=False, geom=None, outmap=None, b_kdiv=0, b_tap_stride=0, stats=None, tile=None, k_split=None,
          bn_cap=128, aux=None, drop_p=0.0, drop_seed=0, split_rounds=None, resid_mask=None, bnr=None, rsub=None,
-         slabs=None, defer_slabs=False):
+         slabs=None, defer_slabs=False, colscale=None, relu_mask_out=None):
     """Raw launcher with automatic tile / split-K choice.  ``slabs``: force (True) or forbid (False) the
     partial-slab split-K path of fp32 outputs (default: deterministic mode or DDL_SPLITK_SLABS);
     ``defer_slabs``: when that path is taken, skip the reduce and return ``(slabs, splits)`` for a
@@ -124,6 +133,13 @@ def gemm(a, b, c, M, N, K, a_mode, b_mode, lda, ldb, ldc, epi, *, alpha=1.0, bet
     must pass a zeroed ``c`` (the gradient arena is zeroed once per step) or
     ``beta == 1`` semantics.
     """
+    if colscale is not None or relu_mask_out is not None:
+        # a BN in the conv's epilogue: only the streaming kernel has it (any M); the launcher refuses the rest
+        if (tile not in (None, TILE_STREAM) or colscale is None or resid is None or alpha != 1.0
+                or not stream_colscale_ok(N, K)):
+            raise ValueError("gemm: colscale / relu_mask_out need the streaming kernel's forward form with a residual "
+                             "(the column scale takes alpha's place: alpha == 1)")
+        tile = TILE_STREAM
     if tile is None:
         if use_stream(M, N, K, a_mode, b_mode, epi, lda, ldc, outmap=outmap, aux=aux, drop_p=drop_p, relu=relu,
                       beta=beta, resid=resid, ldr=ldr):
@@ -162,10 +178,10 @@ def gemm(a, b, c, M, N, K, a_mode, b_mode, lda, ldb, ldc, epi, *, alpha=1.0, bet
         stats = bnr["ws"]
     C().gemm(a, b, out, M, N, K, a_mode, b_mode, lda, ldb, ldc, epi, tile, k_split, alpha, beta, bias, resid, ldr,
              int(relu), geom, outmap, b_kdiv, b_tap_stride, stats, aux, float(drop_p), int(drop_seed), resid_mask,
-             None if bnr is None else bnr["x"], None if bnr is None else bnr.get("mask"),
-             None if bnr is None else bnr["mean"], *(rsub or (0, 0)), None if bnr is None else bnr.get("scale"),
+             None if bnr is None else bnr.get("x"), None if bnr is None else bnr.get("mask"),
+             None if bnr is None else bnr.get("mean"), *(rsub or (0, 0)), None if bnr is None else bnr.get("scale"),
              None if bnr is None else bnr.get("shift"), split_stride,
-             bnr_premask=bool(bnr is not None and bnr.get("premask")))
+             bnr_premask=bool(bnr is not None and bnr.get("premask")), colscale=colscale, relu_mask_out=relu_mask_out)
     if split_stride:
         if defer_slabs:
             return out, math.ceil(K / k_split)
@@ -218,16 +234,24 @@ ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_BWD = 0, 1, 2, 3
 
 
 def linear_fwd(x2, w, bias=None, relu=False, out=None, resid=None, stats=None, act=None, aux=None, drop_p=0.0,
-               drop_seed=0):
+               drop_seed=0, colscale=None, relu_mask_out=None):
     """y[M,N] = x2[M,K] @ w[N,K]^T (+bias) -> act -> dropout (+resid) -> bf16.
 
-    ``act``: ACT_RELU / ACT_GELU (``aux`` receives the bf16 pre-activation)."""
+    ``act``: ACT_RELU / ACT_GELU (``aux`` receives the bf16 pre-activation).  ``colscale`` (fp32 [N]): the
+    accumulator is scaled per column before the bias, ``y = act(acc * colscale + bias + resid)`` — a BatchNorm
+    behind a 1x1 conv applied in its epilogue (scale in ``colscale``, shift in ``bias``); ``relu_mask_out``
+    (uint8 [M * N / 8]) receives the ReLU bit mask of the stored output (bn.hip mode-3 layout).  Both run on the
+    streaming kernel only (``stream_colscale_ok``, with ``resid``); other shapes raise."""
     M, K = x2.shape
     N = w.shape[0]
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
     act = (ACT_RELU if relu else ACT_NONE) if act is None else act
     tiles = math.ceil(M / 64) * math.ceil(N / 64)
+    if colscale is not None or relu_mask_out is not None:
+        return gemm(x2, w, out, M, N, K, KC, KC, x2.stride(0), w.stride(0), out.stride(0), EPI_BF16, bias=bias, relu=act,
+                    resid=resid, ldr=(resid.stride(0) if resid is not None else 0), stats=stats, aux=aux, drop_p=drop_p,
+                    drop_seed=drop_seed, colscale=colscale, relu_mask_out=relu_mask_out)
     if (K >= 1024 and tiles <= _SKINNY_FWD_TILES and act <= ACT_RELU and resid is None and stats is None and aux is None
             and not drop_p and N % 8 == 0 and out.is_contiguous() and x2.device.type == "cuda" and not _det.enabled()):
         # a few output tiles over a long reduction (a Dense on a flattened feature map at a small batch:
@@ -277,7 +301,7 @@ def linear_dgrad(dy, w, out=None, resid=None, gelu_pre=None, stats=None, resid_m
     BatchNorm-backward partial sums of the output (``GemmParams.bnr_*``) into ``ws`` and
     ``bnr["done"]`` is set — the consumer BN then skips its reduce sweep.  ``bnr["premask"]`` (with
     ``"mask"``): the output is stored under the mask and ``ws`` gets the sum of the masked gradient only
-    (``GemmParams.bnr_premask``).  Where no kernel can (mode 2 with a residual on the streaming kernel other
+    (``GemmParams.bnr_premask``); ``"x"`` and ``"mean"`` are not read then and may be absent.  Where no kernel can (mode 2 with a residual on the streaming kernel other
     than the [M, 256] x [256, 64] one, split-K) ``bnr`` is left untouched.  ``wt``: ``w.t()`` contiguous,
     when the caller has it already.  ``rsub = (H, W)``: the rows are an
     [N][H][W] grid and ``resid`` lives on its stride-2 subgrid (``GemmParams.rsub_h``)."""
@@ -342,7 +366,8 @@ def linear_dgrad(dy, w, out=None, resid=None, gelu_pre=None, stats=None, resid_m
 def _bnr_plain_ok(bnr, stats, resid, gelu_pre, ncols) -> bool:
     """The LDS-DMA GEMM's EPI_BF16_BNR epilogue can take this data-gradient's BN-backward reduce (a residual
     included: 8-B aligned rows of 4-element multiples, as its 4-column fragment loads read it)."""
-    return (bnr is not None and stats is None and gelu_pre is None and ncols % 8 == 0 and bnr["x"].is_contiguous()
+    return (bnr is not None and stats is None and gelu_pre is None and ncols % 8 == 0
+            and (bnr["x"].is_contiguous() if bnr.get("x") is not None else bool(bnr.get("premask")))
             and (resid is None or (resid.stride(0) % 4 == 0 and resid.data_ptr() % 8 == 0)))
 
 

@@ -26,7 +26,7 @@ class _StatsPool:
     launches per BN layer; the buffer grows to the largest per-step demand seen."""
 
     def __init__(self):
-        self.buf, self.used, self.demand = {}, {}, {}
+        self.buf, self.used, self.demand, self.epoch = {}, {}, {}, {}
 
     @staticmethod
     def _key(device):
@@ -58,6 +58,7 @@ class _StatsPool:
             dirty = buf[: self.used[key]]
         self.used[key] = 0
         self.demand[key] = 0
+        self.epoch[key] = self.epoch.get(key, 0) + 1
         return dirty
 
 
@@ -72,6 +73,12 @@ def new_stats_workspace(C_, device):
     if torch.device(device).type == "cuda":
         return _POOL.get(C_, device)
     return torch.zeros((SHARDS, 2, C_), dtype=torch.float32, device=device)
+
+
+def pool_epoch(device) -> int:
+    """Resets of the statistics pool so far: memory taken from it stays untouched while this does not change
+    (the pool hands no range out twice between two resets), so a forward may leave a workspace for its backward."""
+    return _POOL.epoch.get(_POOL._key(device), 0)
 
 
 def partials_workspace(M, C_, device):

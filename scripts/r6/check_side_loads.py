@@ -18,7 +18,9 @@ KERNELS = ["ILi16ELi256ELi1ELb1ELi1E", "ILi16ELi256ELi0ELb1ELi1E", "ILi16ELi256E
            "ILi16ELi256ELi1ELb0ELi1E", "ILi16ELi256ELi1ELb1ELi0E", "ILi32ELi256ELi1ELb1ELi0E", "ILi16ELi64ELi1ELb1ELi1E",
            "ILi32ELi64ELi1ELb1ELi1E", "ILi16ELi128ELi1ELb1ELi1E", "ILi32ELi128ELi1ELb1ELi1E", "ILi32ELi64ELi1ELb0ELi2E",
            "ILi32ELi128ELi1ELb0ELi2E", "ILi32ELi64ELi1ELb1ELi0E", "ILi64ELi64ELi1ELb1ELi0E", "ILi32ELi128ELi1ELb1ELi0E",
-           "ILi16ELi128ELi1ELb1ELi0E", "ILi32ELi64ELi0ELb1ELi1E"]
+           "ILi16ELi128ELi1ELb1ELi0E", "ILi32ELi64ELi0ELb1ELi1E",
+           # bn3 in conv3's epilogue (column scale + ReLU-mask byte stores)
+           "ILi64ELi64ELi0ELb1ELi0ELb1E", "ILi32ELi128ELi0ELb1ELi0ELb1E", "ILi32ELi256ELi0ELb1ELi0ELb1E"]
 _LOAD = re.compile(r"\s*global_load_(?:ushort|ubyte|dwordx2|dwordx4|dword)\s+(v\[\d+:\d+\]|v\d+),")
 _ADDR = re.compile(r"//\s*([0-9A-Fa-f]+):")
 
