@@ -60,7 +60,9 @@ void gemm(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int64_t
           c10::optional<at::Tensor> bnr_mean, int64_t rsub_h, int64_t rsub_w, c10::optional<at::Tensor> bnr_scale, c10::optional<at::Tensor> bnr_shift, int64_t split_stride,
           int64_t zcount, int64_t za, int64_t zb, int64_t zc, int64_t zbias, std::vector<int64_t> cls_tap0,
           std::vector<int64_t> cls_nt, std::vector<int64_t> cls_coff, bool bnr_premask,
-          c10::optional<at::Tensor> colscale, c10::optional<at::Tensor> relu_mask_out) {
+          c10::optional<at::Tensor> colscale, c10::optional<at::Tensor> relu_mask_out,
+          c10::optional<at::Tensor> a2, c10::optional<at::Tensor> b2, int64_t lda2, int64_t ldb2,
+          c10::optional<at::Tensor> colscale2, c10::optional<at::Tensor> bias2) {
   CHECK_CUDA(a);
   CHECK_CUDA(b);
   CHECK_CUDA(c);
@@ -240,7 +242,50 @@ void gemm(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int64_t
     p.bnr_mask = bnr_mask->data_ptr<uint8_t>();
     p.bnr_premask = 1;
   }
-  if (colscale || relu_mask_out) {  // a BN applied in the epilogue of the 1x1 conv in front of it (GemmParams::colscale)
+  const bool dual = a2 || b2 || colscale2 || bias2;
+  if (dual) {  // a second product in the same output (GemmParams::a2): conv3 + bn3 and the projection shortcut + BN
+    TORCH_CHECK(tile == kTileStream && a2.has_value() && b2.has_value() && colscale.has_value() && colscale2.has_value() &&
+                    a_mode == OP_KC && b_mode == OP_KC && K == 64 && N % 128 == 0 && !resid && !resid_mask && !stats &&
+                    !bnr_x && !bnr_mask && !bnr_premask && rsub_h == 0 && alpha == 1.0 && !geom && !outmap && zcount <= 1 &&
+                    cls_nt.empty() && split_stride == 0,
+                "gemm: a second product (a2 / b2 / colscale2 / bias2) runs on the streaming kernel with K = 64 per "
+                "product, N % 128 == 0, K-contiguous operands and both column scales, without a residual, statistics, "
+                "a BN-backward reduction or alpha");
+    CHECK_CUDA(*a2);
+    CHECK_CUDA(*b2);
+    CHECK_BF16(*a2);
+    CHECK_BF16(*b2);
+    TORCH_CHECK(lda >= K && lda2 >= K && ldb >= K && ldb2 >= K && lda2 % 8 == 0 && ldb2 % 8 == 0 && ldc >= N &&
+                    ((uintptr_t)a2->data_ptr() % 16) == 0 && ((uintptr_t)b2->data_ptr() % 16) == 0,
+                "gemm: a2 / b2 leading dimensions (>= K, % 8) and 16-B alignment");
+    TORCH_CHECK(a.numel() >= (M - 1) * lda + K && a2->numel() >= (M - 1) * lda2 + K && b.numel() >= (N - 1) * ldb + K &&
+                    b2->numel() >= (N - 1) * ldb2 + K && c.numel() >= (M - 1) * ldc + N,
+                "gemm: an operand of the dual product is too small");
+    for (const auto* t : {&colscale, &colscale2}) {
+      CHECK_CUDA(**t);
+      CHECK_F32(**t);
+      TORCH_CHECK((*t)->is_contiguous() && (*t)->numel() >= N && ((uintptr_t)(*t)->data_ptr() % 16) == 0,
+                  "gemm: colscale / colscale2 [N] fp32, 16-B aligned");
+    }
+    p.colscale = colscale->data_ptr<float>();
+    p.colscale2 = colscale2->data_ptr<float>();
+    if (bias2) {
+      CHECK_CUDA(*bias2);
+      CHECK_F32(*bias2);
+      TORCH_CHECK(bias2->numel() >= N && (uintptr_t)bias2->data_ptr() % 16 == 0, "gemm: bias2 [N] fp32, 16-B aligned");
+      p.bias2 = bias2->data_ptr<float>();
+    }
+    p.a2 = a2->data_ptr();
+    p.b2 = b2->data_ptr();
+    p.lda2 = lda2;
+    p.ldb2 = ldb2;
+    if (relu_mask_out) {
+      TORCH_CHECK(relu_mask_out->is_cuda() && relu_mask_out->scalar_type() == at::kByte && relu_mask_out->is_contiguous() &&
+                      relu_mask_out->numel() >= ((M - 1) * ldc + N + 7) / 8,
+                  "gemm: relu_mask_out must be uint8 [M * ldc / 8]");
+      p.relu_mask_out = relu_mask_out->data_ptr<uint8_t>();
+    }
+  } else if (colscale || relu_mask_out) {  // a BN applied in the epilogue of the 1x1 conv in front of it (GemmParams::colscale)
     TORCH_CHECK(tile == kTileStream && colscale.has_value() && resid.has_value() && b_mode == OP_KC && !stats && !bnr_x &&
                     !bnr_premask && rsub_h == 0 && alpha == 1.0,
                 "gemm: colscale / relu_mask_out run on the streaming kernel's forward form with a residual, without "
@@ -376,7 +421,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("split_stride") = 0, py::arg("zcount") = 1, py::arg("za") = 0, py::arg("zb") = 0, py::arg("zc") = 0,
         py::arg("zbias") = 0, py::arg("cls_tap0") = std::vector<int64_t>{}, py::arg("cls_nt") = std::vector<int64_t>{},
         py::arg("cls_coff") = std::vector<int64_t>{}, py::arg("bnr_premask") = false,
-        py::arg("colscale") = py::none(), py::arg("relu_mask_out") = py::none());
+        py::arg("colscale") = py::none(), py::arg("relu_mask_out") = py::none(), py::arg("a2") = py::none(),
+        py::arg("b2") = py::none(), py::arg("lda2") = 0, py::arg("ldb2") = 0, py::arg("colscale2") = py::none(),
+        py::arg("bias2") = py::none());
   m.def("conv3x3_wgrad", &conv3x3_wgrad, "3x3 stride-1 weight gradient (halo kernel): gw += dW", py::arg("dy"),
         py::arg("x"), py::arg("gw"), py::arg("ws"), py::arg("splits"), py::arg("tpb"), py::arg("pp") = false);
   m.def("conv3x3_wgrad_plan", &conv3x3_wgrad_plan_py,

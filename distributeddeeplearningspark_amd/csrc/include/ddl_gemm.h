@@ -146,6 +146,14 @@ struct GemmParams {
   // the argument layout of every kernel that does not know them is unchanged.)
   const float* colscale;
   uint8_t* relu_mask_out;
+  // a second product in the same output (streaming kernel only, with colscale, without a residual):
+  //   v = (A B^T) * colscale[n] + (A2 B2^T) * colscale2[n] + bias[n] + bias2[n]  (ReLU, relu_mask_out as above)
+  // with both products accumulated in fp32 on their own, K = 64 each, both B operands K-contiguous — conv3 + bn3
+  // and the 1x1 stride-1 projection shortcut + its BN of a bottleneck, neither pre-BN tensor written.
+  const void* a2; long lda2;
+  const void* b2; long ldb2;
+  const float* colscale2;
+  const float* bias2;
 };
 
 enum Activation : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_GELU_BWD = 3 };

@@ -62,6 +62,11 @@ int bn_fold_sums(const void* w, long ldw, const float* P, const float* wsg, cons
                  int rows, float* sums, float* s, int Co, int Ci, hipStream_t st);
 int bn_fold_coef(const void* w, long ldw, const float* P, const float* S, const float* s, const float* coef, void* WA,
                  void* WAt, void* Gm, float* kv, float* dW, long lddw, int Co, int Ci, hipStream_t st);
+//   bn_fold_kv:   kv [Ci] = -((sum_p g) WA + s Gm) / M from the bf16 WA [Co][Ci] and Gm [Ci][Ci] (sg = sums[0]): the
+//                 column sums of d y2 = g WA + y2 Gm + kv then vanish up to the GEMMs' own output rounding, as the
+//                 BN's dx demands — for a d y2 with no BN behind it (a projection shortcut's input gradient)
+int bn_fold_kv(const void* WA, const void* Gm, const float* sg, const float* s, long M, float* kv, int Co, int Ci,
+               hipStream_t st);
 // The forward side of the fold (conv3's output is never written; bn_fold.hip):
 //   gram_colsum:       S[Ci][Ci] += y2^T y2, s[Ci] += sum_p y2 in ONE read of y2 [M][ld] bf16 (S, s zeroed by the
 //                      caller; Ci in {64, 128, 256}, ld % 8 == 0; cus: compute units of the device)

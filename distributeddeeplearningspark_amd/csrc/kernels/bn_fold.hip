@@ -367,4 +367,45 @@ int bn_fold_coef(const void* w, long ldw, const float* P, const float* S, const 
   return (int)hipGetLastError();
 }
 
+namespace {
+
+// kv from the ROUNDED matrices the two data-gradient GEMMs read.  The BN's dx has zero column sums, so
+// sum_p d y2 = (sum_p g) WA + s Gm + M kv = 0 fixes kv; evaluated with the bf16 WA and Gm it cancels their rounding,
+// which otherwise leaves sum_p d y2 off by (sum_p g) dWA + s dGm — a per-channel offset that grows with M.  A BN
+// behind d y2 removes it again (conv3 of a bottleneck: bn2's backward); where d y2 IS the block-input gradient
+// (the projection shortcut) it would reach the parameters below.  64 columns per block, the Co + Ci rows split over
+// the block's 16 waves (a column's Co + Ci loads are latency-bound in one thread), double sums.
+constexpr int KVW = 16;
+__global__ __launch_bounds__(64 * KVW) void bn_fold_kv_kernel(const bf16_t* __restrict__ WA, const bf16_t* __restrict__ Gm,
+                                                               const float* __restrict__ sg, const float* __restrict__ s,
+                                                               double inv_m, float* __restrict__ kv, int Co, int Ci) {
+  __shared__ double red[KVW][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int ci = blockIdx.x * 64 + tx;
+  double a = 0.0;
+  if (ci < Ci) {
+#pragma unroll 4
+    for (int co = ty; co < Co; co += KVW) a += (double)sg[co] * (double)bf2f(WA[(long)co * Ci + ci]);
+#pragma unroll 4
+    for (int cj = ty; cj < Ci; cj += KVW) a += (double)s[cj] * (double)bf2f(Gm[(long)cj * Ci + ci]);
+  }
+  red[ty][tx] = a;
+  __syncthreads();
+  if (ty == 0 && ci < Ci) {
+#pragma unroll
+    for (int j = 1; j < KVW; ++j) a += red[j][tx];
+    kv[ci] = (float)(-a * inv_m);
+  }
+}
+
+}  // namespace
+
+int bn_fold_kv(const void* WA, const void* Gm, const float* sg, const float* s, long M, float* kv, int Co, int Ci,
+               hipStream_t st) {
+  if (Co <= 0 || Ci <= 0 || M <= 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(bn_fold_kv_kernel, dim3((Ci + 63) / 64), dim3(64 * KVW), 0, st, (const bf16_t*)WA, (const bf16_t*)Gm, sg,
+                     s, 1.0 / (double)M, kv, Co, Ci);
+  return (int)hipGetLastError();
+}
+
 }  // namespace ddl

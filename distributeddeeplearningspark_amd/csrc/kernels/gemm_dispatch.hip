@@ -19,6 +19,8 @@ int launch_gemm_bf16(const GemmParams& p_in, int epi, int tile, void* stream) {
   p.group_m = 8;
   // the column-scale / ReLU-mask epilogue exists on the streaming kernel only
   if ((p.colscale || p.relu_mask_out) && tile != kTileStream) return (int)hipErrorInvalidValue;
+  // ... and so does the second product (GemmParams::a2)
+  if ((p.a2 || p.b2 || p.colscale2 || p.bias2) && tile != kTileStream) return (int)hipErrorInvalidValue;
   // premask reads neither bnr_x nor the mean: it is routed by the flag and needs the mask bits
   if (p.bnr_premask && (!p.bnr_mask || !p.stats || p.bnr_scale)) return (int)hipErrorInvalidValue;
   // ... without bnr_x only where a pointwise conv's data-gradient runs: the streaming and the plain-A kernels

@@ -88,9 +88,10 @@ __device__ __forceinline__ void wait_tile(int younger_store_tiles) {
 // writes and does not drain vmcnt(0) before every later LDS access — the ring's ordering is the
 // kernel's own counted vmcnt + barrier (and compiler-placed waits for other loads can only be
 // stricter than needed, never weaker, since they ignore these extra VMEM operations).
-template <class CF>
+// DUAL: a row of the tile is [A row | A2 row]: logical chunks below CPR / 2 come from A, the others from A2.
+template <class CF, bool DUAL = false>
 __device__ __forceinline__ void stage_a(const bf16_t* __restrict__ A, long lda, int M, int m0, char* slot, int w,
-                                        int lane) {
+                                        int lane, const bf16_t* __restrict__ A2 = nullptr, long lda2 = 0) {
 #pragma unroll
   for (int i = 0; i < CF::D; ++i) {
     const int blk = i * 4 + w;
@@ -99,6 +100,9 @@ __device__ __forceinline__ void stage_a(const bf16_t* __restrict__ A, long lda, 
     const int c = cp ^ sw<CF::CPR>(r);
     const int gr = min(m0 + r, M - 1);
     const bf16_t* src = A + (long)gr * lda + c * 8;
+    if constexpr (DUAL) {
+      if (c >= CF::CPR / 2) src = A2 + (long)gr * lda2 + (c - CF::CPR / 2) * 8;
+    }
     const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t) reinterpret_cast<uintptr_t>((lds_t*)(slot + blk * 1024)));
     asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory", "m0");
   }
@@ -167,10 +171,14 @@ template <bool ASM> __device__ __forceinline__ unsigned sld8(const void* p) {
 // gradient is accumulated: neither bnr_x nor bnr_mean is read
 // CSM (GemmParams::colscale / relu_mask_out): v = acc * colscale[n] + bias[n] instead of acc * alpha + bias[n],
 // and the read-out stores one byte of ReLU mask bits (taken from the stored bf16 values) per 16-B vector
-template <int WN, int K, int BMODE, bool RES, int BNR = 0, bool CSM = false>
+// DUAL (GemmParams::a2 ..., with CSM, without RES): two products of K / 2 each in separate fp32 accumulators,
+// v = acc * colscale[n] + acc2 * colscale2[n] + bias[n] + bias2[n] — a bottleneck's conv3 + bn3 and its 1x1
+// projection shortcut + BN as one output.  The A tile is [A row | A2 row], the k-steps of the upper half read B2
+template <int WN, int K, int BMODE, bool RES, int BNR = 0, bool CSM = false, bool DUAL = false>
 __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const GemmParams p) {
   using namespace gst;
   using CF = Cfg<WN, K, CSM>;
+  static_assert(!DUAL || (CSM && !RES && BNR == 0 && BMODE == OP_KC && CF::KS % 2 == 0), "dual form");
   // side-operand loads as counted asm (see sld128) on every ring: on the two-slot K = 256 rings it keeps the
   // refill DMA in flight through the epilogue (ResNet-50 +0.9 %); on the deeper rings it measured equal to
   // compiler-tracked loads end to end (profiles/r6/stream_side_loads/)
@@ -184,6 +192,7 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
   const int mt = (p.M + BM - 1) / BM;
   const int nloc = ((int)blockIdx.x < mt) ? (mt - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
   const bf16_t* __restrict__ A = reinterpret_cast<const bf16_t*>(p.a);
+  const bf16_t* __restrict__ A2 = DUAL ? reinterpret_cast<const bf16_t*>(p.a2) : nullptr;
 
   // B slice in registers: bfr[rn][ks][j] = B(n0 + WN*w + 16rn + (lane&15), 32ks + 8(lane>>4) + j)
   bf16x8 bfr[CF::RN][CF::KS];
@@ -195,7 +204,12 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
       for (int ks = 0; ks < CF::KS; ++ks) {
         const int n = n0 + WN * w + 16 * rn + (lane & 15);
         const int k = 32 * ks + 8 * (lane >> 4);
-        if constexpr (BMODE == OP_KC) {
+        if constexpr (DUAL) {
+          if (ks < CF::KS / 2)
+            bfr[rn][ks] = *reinterpret_cast<const bf16x8*>(B + (long)n * p.ldb + k);
+          else
+            bfr[rn][ks] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(p.b2) + (long)n * p.ldb2 + k - K / 2);
+        } else if constexpr (BMODE == OP_KC) {
           bfr[rn][ks] = *reinterpret_cast<const bf16x8*>(B + (long)n * p.ldb + k);
         } else {
           s16x8 v;
@@ -214,6 +228,15 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
     bias_r[rn][1] = bv.y;
     bias_r[rn][2] = bv.z;
     bias_r[rn][3] = bv.w;
+    if constexpr (DUAL) {
+      if (p.bias2) {
+        const float4 b2 = *reinterpret_cast<const float4*>(p.bias2 + n0 + WN * w + 16 * rn + 4 * (lane >> 4));
+        bias_r[rn][0] += b2.x;
+        bias_r[rn][1] += b2.y;
+        bias_r[rn][2] += b2.z;
+        bias_r[rn][3] += b2.w;
+      }
+    }
   }
   float csc_r[CSM ? CF::RN : 1][4];
   if constexpr (CSM) {
@@ -226,11 +249,23 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
       csc_r[rn][3] = cv.w;
     }
   }
+  float csc2_r[DUAL ? CF::RN : 1][4];
+  if constexpr (DUAL) {
+#pragma unroll
+    for (int rn = 0; rn < CF::RN; ++rn) {
+      const float4 cv = *reinterpret_cast<const float4*>(p.colscale2 + n0 + WN * w + 16 * rn + 4 * (lane >> 4));
+      csc2_r[rn][0] = cv.x;
+      csc2_r[rn][1] = cv.y;
+      csc2_r[rn][2] = cv.z;
+      csc2_r[rn][3] = cv.w;
+    }
+  }
   wait_vm<0>();  // B fragments and bias in registers before the LDS-DMA ring starts
   auto tile_m0 = [&](int i) { return min((int)blockIdx.x + i * (int)gridDim.x, mt - 1) * BM; };
 
 #pragma unroll
-  for (int s = 0; s < CF::NBUF - 1; ++s) stage_a<CF>(A, p.lda, p.M, tile_m0(s), smem + s * CF::TILE, w, lane);
+  for (int s = 0; s < CF::NBUF - 1; ++s)
+    stage_a<CF, DUAL>(A, p.lda, p.M, tile_m0(s), smem + s * CF::TILE, w, lane, A2, p.lda2);
 
   float s1[8], s2[8];
 #pragma unroll
@@ -307,7 +342,7 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
       }
     }
     const int ahead = i + CF::NBUF - 1;
-    stage_a<CF>(A, p.lda, p.M, tile_m0(ahead), smem + (ahead % CF::NBUF) * CF::TILE, w, lane);
+    stage_a<CF, DUAL>(A, p.lda, p.M, tile_m0(ahead), smem + (ahead % CF::NBUF) * CF::TILE, w, lane, A2, p.lda2);
     if constexpr (CSM) {  // without a mask output the read-outs issue S stores, not SV (block-uniform)
       if (p.relu_mask_out) wait_tile<CF, CF::SV>(min(i, CF::NBUF - 1));
       else wait_tile<CF>(min(i, CF::NBUF - 1));
@@ -322,6 +357,13 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
     for (int mb = 0; mb < BM / 16; ++mb)
 #pragma unroll
       for (int rn = 0; rn < CF::RN; ++rn) acc[mb][rn] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc2[DUAL ? BM / 16 : 1][DUAL ? CF::RN : 1];  // DUAL: the product of the upper K half (A2 x B2)
+    if constexpr (DUAL) {
+#pragma unroll
+      for (int mb = 0; mb < BM / 16; ++mb)
+#pragma unroll
+        for (int rn = 0; rn < CF::RN; ++rn) acc2[mb][rn] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int ks = 0; ks < CF::KS; ++ks)
 #pragma unroll
@@ -330,7 +372,15 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
         const int c = 4 * ks + (lane >> 4);
         const bf16x8 a = *reinterpret_cast<const bf16x8*>(abuf + r * (K * 2) + ((c ^ sw<CF::CPR>(r)) << 4));
 #pragma unroll
-        for (int rn = 0; rn < CF::RN; ++rn) acc[mb][rn] = mfma16x16x32(bfr[rn][ks], a, acc[mb][rn]);
+        for (int rn = 0; rn < CF::RN; ++rn) {
+          if constexpr (DUAL) {
+            if (ks >= CF::KS / 2) {
+              acc2[mb][rn] = mfma16x16x32(bfr[rn][ks], a, acc2[mb][rn]);
+              continue;
+            }
+          }
+          acc[mb][rn] = mfma16x16x32(bfr[rn][ks], a, acc[mb][rn]);
+        }
       }
 
     // counted waits (asm side loads): the residual before the epilogue math, with the BN-reduce loads (issued
@@ -358,7 +408,8 @@ __global__ __launch_bounds__(gst::THREADS, 2) void gemm_stream_kernel(const Gemm
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          if constexpr (CSM) v[e] = fmaf(acc[mb][rn][e], csc_r[rn][e], bias_r[rn][e]);
+          if constexpr (DUAL) v[e] = fmaf(acc[mb][rn][e], csc_r[rn][e], fmaf(acc2[mb][rn][e], csc2_r[rn][e], bias_r[rn][e]));
+          else if constexpr (CSM) v[e] = fmaf(acc[mb][rn][e], csc_r[rn][e], bias_r[rn][e]);
           else v[e] = fmaf(acc[mb][rn][e], p.alpha, bias_r[rn][e]);
         }
         if constexpr (RES) {
@@ -608,7 +659,30 @@ int gemm_stream_panel(int N, int K) {
   return 0;
 }
 
+// conv3 + bn3 and the 1x1 projection shortcut + BN of a bottleneck as one output (GemmParams::a2): K = 64 per
+// product on the 128-wide panel (two accumulator sets: the 256-wide panel would spill), both operands KC, no
+// residual / statistics / BN-backward reduce / alpha; everything else is refused and nothing is launched
+static int launch_dual(const GemmParams& p, int epi, hipStream_t s) {
+  using CF = gst::Cfg<32, 128, true>;
+  auto al16 = [](const void* q) { return (uintptr_t)q % 16 == 0; };
+  const bool ok = p.a && p.a2 && p.b && p.b2 && p.colscale && p.colscale2 && p.K == 64 && p.N > 0 && p.N % CF::NB == 0 &&
+                  epi == EPI_BF16 && p.a_mode == OP_KC && p.b_mode == OP_KC && !p.resid && !p.resid_mask && !p.stats &&
+                  !p.bnr_x && !p.bnr_premask && !p.bnr_mask && !p.rsub_h && p.alpha == 1.f && p.beta == 0.f &&
+                  !p.om.enabled && !p.aux && !p.drop_thresh && (p.relu == ACT_NONE || p.relu == ACT_RELU) &&
+                  p.k_split >= p.K && !p.split_stride && p.zcount <= 1 && !p.zcls && p.lda % 8 == 0 && p.lda2 % 8 == 0 &&
+                  p.ldb % 8 == 0 && p.ldb2 % 8 == 0 && p.ldc % 8 == 0 && p.lda >= 64 && p.lda2 >= 64 && p.ldb >= 64 &&
+                  p.ldb2 >= 64 && p.ldc >= p.N && al16(p.a) && al16(p.a2) && al16(p.b) && al16(p.b2) && al16(p.c) &&
+                  al16(p.colscale) && al16(p.colscale2) && al16(p.bias) && al16(p.bias2);
+  if (!ok) return (int)hipErrorInvalidValue;
+  const int panels = p.N / CF::NB;
+  const int mt = (p.M + gst::BM - 1) / gst::BM;
+  const int gx = std::max(1, std::min(mt, 2 * num_cus() / std::max(1, panels)));
+  hipLaunchKernelGGL((gemm_stream_kernel<32, 128, OP_KC, false, 0, true, true>), dim3(gx, panels), dim3(gst::THREADS), 0, s, p);
+  return (int)hipGetLastError();
+}
+
 int launch_gemm_stream(const GemmParams& p, int epi, hipStream_t s) {
+  if (p.a2 || p.b2 || p.colscale2 || p.bias2) return launch_dual(p, epi, s);
   int nb = gemm_stream_panel(p.N, p.K);
   if (p.resid && p.K == 128 && nb == 256) nb = 128;  // 256-wide panel + residual prefetch would spill
   // the fused BN-backward reduction prefetches x and the mask per read-out vector: narrower panels keep

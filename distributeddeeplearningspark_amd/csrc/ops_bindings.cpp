@@ -200,6 +200,20 @@ void bn_fold_coef_(const at::Tensor& w, const at::Tensor& P, const at::Tensor& S
                       dW.data_ptr<float>(), dW.stride(0), (int)Co, (int)Ci, cur_stream()));
 }
 
+// kv [Ci] <- -((sum g) WA + s Gm) / M from the rounded bf16 matrices (ddl_ops.h)
+void bn_fold_kv_(const at::Tensor& WA, const at::Tensor& Gm, const at::Tensor& sg, const at::Tensor& s, int64_t M,
+                 const at::Tensor& kv) {
+  GPU(WA); BF16(WA); BF16(Gm); F32(sg); F32(s); F32(kv);
+  CK(WA.dim() == 2 && WA.is_contiguous() && Gm.is_contiguous() && sg.is_contiguous() && s.is_contiguous() &&
+         kv.is_contiguous() && Gm.is_cuda() && sg.is_cuda() && s.is_cuda() && kv.is_cuda(),
+     "bn_fold_kv: contiguous GPU tensors, WA [Co, Ci]");
+  const int64_t Co = WA.size(0), Ci = WA.size(1);
+  CK(Gm.numel() == Ci * Ci && sg.numel() >= Co && s.numel() == Ci && kv.numel() == Ci && M > 0, "bn_fold_kv: shapes");
+  at::DeviceGuard g(WA.device());
+  HIP_OK(bn_fold_kv(WA.data_ptr(), Gm.data_ptr(), sg.data_ptr<float>(), s.data_ptr<float>(), M, kv.data_ptr<float>(),
+                    (int)Co, (int)Ci, cur_stream()));
+}
+
 void bn_bwd_dx_(const at::Tensor& dy, const at::Tensor& x, c10::optional<at::Tensor> y,
                 c10::optional<at::Tensor> scale, c10::optional<at::Tensor> shift, const at::Tensor& coef,
                 const at::Tensor& dx, c10::optional<at::Tensor> dres, int64_t C, int64_t mode) {
@@ -786,6 +800,7 @@ void register_ops(py::module& m) {
   m.def("bn_bwd_finalize", &bn_bwd_finalize_);
   m.def("bn_fold_sums", &bn_fold_sums_);
   m.def("bn_fold_coef", &bn_fold_coef_);
+  m.def("bn_fold_kv", &bn_fold_kv_);
   m.def("gram_colsum", &gram_colsum_);
   m.def("bn_fold_fwd_stats", &bn_fold_fwd_stats_);
   m.def("bn_bwd_dx", &bn_bwd_dx_);

@@ -18,6 +18,10 @@ What the fusion buys over composing per-op autograd nodes:
     needs both anyway), and conv3 applies bn3, the shortcut and the ReLU in its own epilogue, writing the block
     output and the ReLU bit mask (``_convbn3_fold_forward``).  A backward that cannot fold recomputes conv3's
     output first (``_recompute_yc``);
+  * a projection block whose shortcut conv is 1x1 / stride 1 (``_FOLD_DOWN``, ResNet-50's ``layer1.0``) folds both
+    bn3 and the shortcut's BN the same way: both BNs' statistics from the Gram matrices of the 4x narrower y2 and
+    x, ONE two-product GEMM that writes the block output and its mask (``_fold_down_forward``) — neither pre-BN
+    tensor is written — and ``fold_conv_bn_backward`` once per unit on the same pre-masked gradient;
   * all workspaces come from the per-step statistics pool;
   * parameter-gradient hooks (for the overlapped RCCL all-reduce) fire per layer in
     backward order as soon as each layer's gradients are final.
@@ -190,19 +194,27 @@ class _BottleneckFn(torch.autograd.Function):
     def forward(ctx, x, anchor, block):
         ctx.prev = _producer_of(x) if _FUSE_BNR else None  # the BN whose output is this block's input
         x = x.contiguous()
-        # the downsample BN is not applied on its own: its scale/shift normalise the shortcut inside
-        # the block-output apply sweep (one write + one read of the shortcut tensor saved)
-        s_down = convbn_forward(block.down, x, relu=False, apply=False) if block.down is not None else None
-        sc = s_down.yc if s_down is not None else x
-        s1 = convbn_forward(block.c1, x, relu=True)
-        s2 = convbn_forward(block.c2, s1.y, relu=True)
-        g3 = _fold_fwd_geometry(block.c3, s2.y) if s_down is None else None
-        if g3 is not None:
-            s3 = _convbn3_fold_forward(block.c3, s2.y, sc, g3)
+        gdn = _fold_down_geometry(block, x) if block.down is not None else None
+        if gdn is not None:
+            # both pre-BN tensors of the block's tail stay unwritten: the shortcut conv runs inside the output GEMM
+            s1 = convbn_forward(block.c1, x, relu=True)
+            s2 = convbn_forward(block.c2, s1.y, relu=True)
+            s_down, s3 = _fold_down_forward(block, x, s2.y, *gdn)
+            s3.fold = True  # the next block's conv1 data-gradient pre-masks (backward: fold_dn)
         else:
-            s3 = convbn_forward(block.c3, s2.y, resid=sc, relu=True,
-                                res_affine=None if s_down is None else (s_down.scale, s_down.shift))
-        s3.fold = s_down is None and s3.mode == 3 and _fold_gate(s3.g)
+            # the downsample BN is not applied on its own: its scale/shift normalise the shortcut inside
+            # the block-output apply sweep (one write + one read of the shortcut tensor saved)
+            s_down = convbn_forward(block.down, x, relu=False, apply=False) if block.down is not None else None
+            sc = s_down.yc if s_down is not None else x
+            s1 = convbn_forward(block.c1, x, relu=True)
+            s2 = convbn_forward(block.c2, s1.y, relu=True)
+            g3 = _fold_fwd_geometry(block.c3, s2.y) if s_down is None else None
+            if g3 is not None:
+                s3 = _convbn3_fold_forward(block.c3, s2.y, sc, g3)
+            else:
+                s3 = convbn_forward(block.c3, s2.y, resid=sc, relu=True,
+                                    res_affine=None if s_down is None else (s_down.scale, s_down.shift))
+            s3.fold = s_down is None and s3.mode == 3 and _fold_gate(s3.g)
         ctx.block, ctx.states = block, (s_down, s1, s2, s3)
         ctx.save_for_backward(x)
         ctx.needs_dx = ctx.needs_input_grad[0]
@@ -229,26 +241,39 @@ class _BottleneckFn(torch.autograd.Function):
         pre3 = s3.pre_reduced
         fold = (_FOLD_BN3 and s3.fold and not _det.enabled() and pre3 is not None and pre3[2]
                 and _same_tensor(pre3[1], dout) and b.c3.bn.gamma is not None)
-        if fold:
+        # projection block whose forward folded both BNs (_fold_down_forward): the same, once per unit; the
+        # shortcut's turn comes where its backward always ran (below), on the same gradient and column sums
+        fold_dn = fold and s_down is not None and s_down.gram is not None
+        fold = fold and s_down is None
+        ws_g = None
+        if fold_dn:
+            s3.pre_reduced = None
+            ws_g = pre3[0]
+            bnr2 = _bnr_mode2(s2, dout.device)
+            d2 = _fold_unit_backward(b.c3, s3, s2.y, dout, ws_g, bnr2)
+        elif fold:
             s3.pre_reduced = None
             bnr2 = _bnr_mode2(s2, dout.device)
             d2 = _fold_bn3_backward(b.c3, s3, s2, dout, pre3[0], bnr2)
             dsc = dout  # pre-masked: it is the shortcut's gradient as it stands
-        elif s3.yc is None:
-            # the forward never wrote conv3's output and this backward does not fold (a second consumer, a
-            # producer that did not pre-mask, the network's last block): recompute it, then the sweeps as before
-            _recompute_yc(b.c3, s3, s2)
-            d3c, dsc = bn_backward(b.c3, s3, dout, want_dres=not masked_sc)
-        elif fuse_down:
-            Cd = s_down.yc.shape[-1]
-            ws_d = partials_workspace(s_down.yc.numel() // Cd, Cd, dout.device)
-            d3c, dsc = bn_backward(b.c3, s3, dout, False, red2=(s_down.yc, s_down.mean, ws_d))
         else:
-            d3c, dsc = bn_backward(b.c3, s3, dout, want_dres=not masked_sc)
+            if s3.yc is None:
+                # the forward never wrote conv3's output (nor the shortcut conv's, in a folding projection block)
+                # and this backward does not fold (a second consumer, a producer that did not pre-mask, the
+                # network's last block): recompute, then the sweeps as before
+                _recompute_yc(b.c3, s3, s2)
+                if s_down is not None and s_down.yc is None:
+                    _recompute_yc(b.down, s_down, x)
+            if fuse_down:
+                Cd = s_down.yc.shape[-1]
+                ws_d = partials_workspace(s_down.yc.numel() // Cd, Cd, dout.device)
+                d3c, dsc = bn_backward(b.c3, s3, dout, False, red2=(s_down.yc, s_down.mean, ws_d))
+            else:
+                d3c, dsc = bn_backward(b.c3, s3, dout, want_dres=not masked_sc)
         # the data-gradients of conv3 and conv2 produce bn2's / bn1's output gradients: their epilogues also
         # accumulate those BNs' backward partial sums (ReLU mask recomputed from yc), so bn_backward skips the
         # reduce sweep wherever the kernel that ran could take it (bnr["done"])
-        if not fold:
+        if not (fold or fold_dn):
             bnr2 = _bnr_mode2(s2, dout.device)
             d2 = conv_backward(b.c3, s3, d3c, s2.y, True, bnr=bnr2)
         _take_reduced(s2, bnr2, d2)
@@ -258,7 +283,11 @@ class _BottleneckFn(torch.autograd.Function):
         _take_reduced(s1, bnr1, d1)
         d1c, _ = bn_backward(b.c1, s1, d1, False)
         rsub = None
-        if s_down is not None:
+        if fold_dn:
+            # [M, Ci] as it stands: conv1's data-gradient adds it as the plain residual
+            # (no BN behind it takes a per-channel offset out again: its column sums are made to vanish)
+            dsc = _fold_unit_backward(b.down, s_down, x, dout, ws_g, None, need_dx=ctx.needs_dx, exact_colsum=True)
+        elif s_down is not None:
             if fuse_down:
                 ddc, _ = bn_backward(b.down, s_down, dout, False, dy_mask=s3.mask, reduced=ws_d)
             else:
@@ -366,44 +395,112 @@ def _convbn3_fold_forward(unit, x2, resid, g):
     """conv3 + bn3 + identity shortcut + ReLU of a folding block without conv3's output: S = x2^T x2 and
     s = sum x2 (``gram_colsum``) -> bn3's batch sums (``bn_fold_fwd_stats``) -> ``bn_finalize`` as ever -> ONE
     GEMM that applies scale / shift / shortcut / ReLU in its epilogue and writes y and the ReLU bit mask."""
-    conv, bn = unit.conv, unit.bn
     M, Co, Ci = g.M, g.Co, g.Ci
     dev = x2.device
     x2m = x2.view(M, Ci)
-    # S | s: zeroed fp32 from the per-step statistics pool, which hands no memory out twice within a step, so
-    # they live until this step's backward (the epoch tells a backward that runs after a later reset)
-    ps = new_stats_workspace(-(-(Ci * Ci + Ci) // 64), dev).view(-1)
-    S, s = ps[: Ci * Ci].view(Ci, Ci), ps[Ci * Ci : Ci * Ci + Ci]
-    C().gram_colsum(x2m, S, s)
-    stats = new_stats_workspace(Co, dev)
-    w = conv.kernel.data.view(Co, Ci)
-    C().bn_fold_fwd_stats(w, S, s, M, stats)
-    gamma = None if bn.gamma is None else bn.gamma.master
-    beta = None if bn.beta is None else bn.beta.master
-    rm, rv = bn._states["moving_mean"], bn._states["moving_variance"]
-    scale, shift, mean, invstd = torch.empty(4, Co, dtype=torch.float32, device=dev).unbind(0)
-    C().bn_finalize(stats, M, Co, gamma, beta, bn.epsilon, 1.0 - bn.momentum, rm, rv, mean, invstd, scale, shift)
-    st = _ConvBNState()
-    st.g, st.yc = g, None
+    st = _fold_fwd_stats(unit, x2m, g)
     st.mask = torch.empty(-(-M * Co // 32) * 4, dtype=torch.uint8, device=dev)
     y = torch.empty((g.N, g.H, g.W, Co), dtype=torch.bfloat16, device=dev)
-    G.linear_fwd(x2m, w, bias=shift, relu=True, out=y.view(M, Co), resid=resid.view(M, Co), colscale=scale,
-                 relu_mask_out=st.mask)
-    st.y, st.mean, st.invstd, st.scale, st.shift, st.mode = y, mean, invstd, scale, shift, 3
-    st.gram = (S, s, pool_epoch(dev))
+    G.linear_fwd(x2m, unit.conv.kernel.data.view(Co, Ci), bias=st.shift, relu=True, out=y.view(M, Co),
+                 resid=resid.view(M, Co), colscale=st.scale, relu_mask_out=st.mask)
+    st.y, st.mode = y, 3
     return st
 
 
 def _recompute_yc(unit, s3, s2):
-    """conv3's output of a block whose forward did not write it (plain forward GEMM), for the unfolded sweeps."""
+    """The 1x1 conv output of a unit whose forward did not write it (plain forward GEMM), for the unfolded sweeps:
+    conv3 from ``s2`` (the state in front of it), or a folding projection block's shortcut conv from ``s2`` = the
+    block input itself."""
     geo = s3.g
+    xin = s2.y if isinstance(s2, _ConvBNState) else s2
     w = unit.conv.kernel.data.view(geo.Co, geo.Ci)
-    yc = torch.empty((geo.N, geo.H, geo.W, geo.Co), dtype=torch.bfloat16, device=s2.y.device)
-    G.linear_fwd(s2.y.view(geo.M, geo.Ci), w, out=yc.view(geo.M, geo.Co))
+    yc = torch.empty((geo.N, geo.H, geo.W, geo.Co), dtype=torch.bfloat16, device=xin.device)
+    G.linear_fwd(xin.view(geo.M, geo.Ci), w, out=yc.view(geo.M, geo.Co))
     s3.yc = yc
 
 
-def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbeta, bnr2=None, out=None, gram=None):
+# a projection bottleneck whose shortcut conv is 1x1 / stride 1 folds bn3 AND the shortcut's BN (forward and
+# backward); only effective with _FOLD_BN3 and _FOLD_BN3_FWD; monkeypatchable
+_FOLD_DOWN = True
+# its own size gate on the [M, Co] block output (ResNet-50 at batch 256: layer1.0 only, 2^27.6 elements)
+_FOLD_DOWN_MIN_ELEMS = 1 << 27
+
+
+def _pointwise_geometry(conv, xshape):
+    N, H, W, Ci = xshape
+    kh, kw = conv.kernel_size
+    if (kh, kw) != (1, 1):
+        return None
+    p = conv.padding if isinstance(conv.padding, tuple) else (0, 0)
+    g = CV.geometry(N, H, W, Ci, conv.filters, kh, kw, conv.strides, p, conv.dilation_rate)
+    return g if g.is_pointwise else None
+
+
+def _fold_down_geometry(block, x):
+    """(conv3's geometry, the shortcut conv's) when this projection block folds both BNs of its tail, else None:
+    the flags, not in deterministic mode, both BNs with a scale, both convs 1x1 / stride 1 over the same pixels
+    with 64 input channels (the two-product GEMM's shape), a stride-1 main path, and the size gate."""
+    if not (_FOLD_BN3 and _FOLD_BN3_FWD and _FOLD_DOWN) or _det.enabled() or x.device.type != "cuda":
+        return None
+    if block.c3.bn.gamma is None or block.down.bn.gamma is None or x.dtype != torch.bfloat16:
+        return None
+    N, H, W, _ = x.shape
+    if any(tuple(u.conv.strides) != (1, 1) for u in (block.c1, block.c2)):
+        return None
+    gd = _pointwise_geometry(block.down.conv, x.shape)
+    g3 = _pointwise_geometry(block.c3.conv, (N, H, W, block.c2.conv.filters))
+    if gd is None or g3 is None or gd.Co != g3.Co or gd.Co % 128:
+        return None
+    if not G.stream_dual_ok(g3.Co, g3.Ci, gd.Ci) or g3.M * g3.Co < _FOLD_DOWN_MIN_ELEMS:
+        return None
+    return g3, gd
+
+
+def _fold_fwd_stats(unit, xm, g):
+    """State of a 1x1 conv + BN whose output is not written: the BN's batch statistics from S = x^T x and s = sum x
+    (``gram_colsum`` -> ``bn_fold_fwd_stats`` -> ``bn_finalize`` as ever, running statistics included)."""
+    conv, bn = unit.conv, unit.bn
+    M, Co, Ci = g.M, g.Co, g.Ci
+    dev = xm.device
+    # S | s: zeroed fp32 from the per-step statistics pool, which hands no memory out twice within a step, so
+    # they live until this step's backward (the epoch tells a backward that runs after a later reset)
+    ps = new_stats_workspace(-(-(Ci * Ci + Ci) // 64), dev).view(-1)
+    S, s = ps[: Ci * Ci].view(Ci, Ci), ps[Ci * Ci : Ci * Ci + Ci]
+    C().gram_colsum(xm, S, s)
+    stats = new_stats_workspace(Co, dev)
+    C().bn_fold_fwd_stats(conv.kernel.data.view(Co, Ci), S, s, M, stats)
+    gamma = None if bn.gamma is None else bn.gamma.master
+    beta = None if bn.beta is None else bn.beta.master
+    rm, rv = bn._states["moving_mean"], bn._states["moving_variance"]
+    st = _ConvBNState()
+    st.g, st.yc, st.y, st.mask = g, None, None, None
+    st.scale, st.shift, st.mean, st.invstd = torch.empty(4, Co, dtype=torch.float32, device=dev).unbind(0)
+    C().bn_finalize(stats, M, Co, gamma, beta, bn.epsilon, 1.0 - bn.momentum, rm, rv, st.mean, st.invstd, st.scale,
+                    st.shift)
+    st.gram = (S, s, pool_epoch(dev))
+    return st
+
+
+def _fold_down_forward(block, x, y2, g3, gd):
+    """Tail of a folding projection block: y = relu(bn3(conv3 y2) + bn_d(conv_d x)) from the two narrow inputs.
+    Returns (shortcut state, bn3 state): neither has a conv output (``yc`` None), both keep their Gram."""
+    M, Co = g3.M, g3.Co
+    if tuple(y2.shape) != (g3.N, g3.H, g3.W, g3.Ci):
+        raise RuntimeError("folding projection block: conv2's output does not match conv3's geometry")
+    y2 = y2.contiguous()
+    s3 = _fold_fwd_stats(block.c3, y2.view(M, g3.Ci), g3)
+    sd = _fold_fwd_stats(block.down, x.view(M, gd.Ci), gd)
+    s3.mask = torch.empty(-(-M * Co // 32) * 4, dtype=torch.uint8, device=x.device)
+    y = torch.empty((g3.N, g3.H, g3.W, Co), dtype=torch.bfloat16, device=x.device)
+    G.linear_dual_fwd(y2.view(M, g3.Ci), block.c3.conv.kernel.data.view(Co, g3.Ci), s3.scale,
+                      x.view(M, gd.Ci), block.down.conv.kernel.data.view(Co, gd.Ci), sd.scale,
+                      shift1=s3.shift, shift2=sd.shift, relu=True, out=y.view(M, Co), relu_mask_out=s3.mask)
+    s3.y, s3.mode, sd.mode = y, 3, 0
+    return sd, s3
+
+
+def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbeta, bnr2=None, out=None, gram=None,
+                          need_dx=True, exact_colsum=False):
     """Backward of ``yc = y2 w^T -> BN`` (a 1x1 conv and the BN behind it) from the BN's output gradient ``g2``
     [M, Co], already under the BN's ReLU mask, and its column sums ``ws_g`` ([32, 2, Co], row [:, 0]): with the
     BN's dx = A g + B yc + K,
@@ -411,7 +508,9 @@ def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbet
     (csrc/kernels/bn_fold.hip) — neither yc nor dx is read or written.  ``dgamma`` / ``dbeta`` accumulate as in
     ``bn_bwd_finalize``; ``bnr2``: fused BN-backward reduce of d2 (``gemm.linear_dgrad``).
     ``gram = (S, s)``: the forward formed them already (``gram_colsum``): neither the S product nor the
-    ``bn_stats`` sweep over y2 is launched.
+    ``bn_stats`` sweep over y2 is launched.  ``need_dx = False``: parameter gradients only (d2 is None).
+    ``exact_colsum``: kv is re-formed from the rounded bf16 WA and Gm (``bn_fold_kv``) so that the column sums of d2
+    vanish as the BN's dx demands; for a d2 with no BN behind it to remove a per-channel offset (a shortcut's).
     Returns (d2 [M, Ci] bf16, sums [2, Co]: sum g and sum g (yc - mean))."""
     M, Co = g2.shape
     Ci = y2.shape[1]
@@ -437,6 +536,10 @@ def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbet
     b16 = torch.empty(2 * Co * Ci + Ci * Ci, dtype=torch.bfloat16, device=dev)
     WA, WAt, Gm = b16[: Co * Ci].view(Co, Ci), b16[Co * Ci : 2 * Co * Ci].view(Ci, Co), b16[2 * Co * Ci :].view(Ci, Ci)
     C().bn_fold_coef(w, P, S, s, coef, WA, WAt, Gm, kv, gw)
+    if not need_dx:
+        return None, sums.view(2, Co)
+    if exact_colsum:
+        C().bn_fold_kv(WA, Gm, sums[:Co], s, M, kv)
     r = G.linear_fwd(y2, Gm, bias=kv)
     if out is None:
         out = torch.empty((M, Ci), dtype=torch.bfloat16, device=dev)
@@ -447,21 +550,31 @@ def fold_conv_bn_backward(w, gw, g2, y2, ws_g, mean, invstd, gamma, dgamma, dbet
 def _fold_bn3_backward(unit, s3, s2, g, ws_g, bnr2):
     """conv3 + bn3 backward of an identity bottleneck from the pre-masked output gradient ``g`` and its column
     sums ``ws_g`` (``fold_conv_bn_backward``).  Returns d2."""
+    return _fold_unit_backward(unit, s3, s2.y, g, ws_g, bnr2)
+
+
+def _fold_unit_backward(unit, st, xin, g, ws_g, bnr2, need_dx=True, exact_colsum=False):
+    """1x1 conv + BN backward of one folding unit (conv3 + bn3 from y2; a projection block's shortcut conv + its BN
+    from the block input) from the pre-masked block-output gradient ``g`` and its column sums ``ws_g``
+    (``fold_conv_bn_backward``), then the unit's gradient hooks.  Returns the unit's input gradient [N, H, W, Ci],
+    or None without ``need_dx``."""
     conv, bn = unit.conv, unit.bn
-    geo = s3.g
+    geo = st.g
     M, Co, Ci = geo.M, geo.Co, geo.Ci
-    d2 = torch.empty((geo.N, geo.H, geo.W, Ci), dtype=torch.bfloat16, device=g.device)
+    dx = torch.empty((geo.N, geo.H, geo.W, Ci), dtype=torch.bfloat16, device=g.device) if need_dx else None
     gram = None
-    if s3.gram is not None and s3.gram[2] == pool_epoch(g.device):  # the pool has not been reset since the forward
-        gram = s3.gram[:2]
-    fold_conv_bn_backward(conv.kernel.data.view(Co, Ci), conv.kernel.grad.view(Co, Ci), g.view(M, Co), s2.y.view(M, Ci),
-                          ws_g, s3.mean, s3.invstd, bn.gamma.master, bn.gamma.grad,
-                          None if bn.beta is None else bn.beta.grad, bnr2=bnr2, out=d2.view(M, Ci), gram=gram)
+    if st.gram is not None and st.gram[2] == pool_epoch(g.device):  # the pool has not been reset since the forward
+        gram = st.gram[:2]
+    fold_conv_bn_backward(conv.kernel.data.view(Co, Ci), conv.kernel.grad.view(Co, Ci), g.view(M, Co), xin.view(M, Ci),
+                          ws_g, st.mean, st.invstd, bn.gamma.master, bn.gamma.grad,
+                          None if bn.beta is None else bn.beta.grad, bnr2=bnr2,
+                          out=None if dx is None else dx.view(M, Ci), gram=gram, need_dx=need_dx,
+                          exact_colsum=exact_colsum)
     if bn.grad_hook is not None:
         bn.grad_hook()
     if conv.grad_hook is not None:  # after the last read of the weights (see conv_backward)
         conv.grad_hook()
-    return d2
+    return dx
 
 
 def _same_tensor(a, b) -> bool:

@@ -271,6 +271,31 @@ def linear_fwd(x2, w, bias=None, relu=False, out=None, resid=None, stats=None, a
                 drop_seed=drop_seed)
 
 
+def stream_dual_ok(N: int, K1: int, K2: int) -> bool:
+    """The streaming kernel has the two-product form (``linear_dual_fwd``) for this shape: K = 64 per product on
+    the 128-wide panel."""
+    return K1 == 64 and K2 == 64 and N > 0 and N % 128 == 0
+
+
+def linear_dual_fwd(x1, w1, scale1, x2, w2, scale2, shift1=None, shift2=None, relu=True, out=None, relu_mask_out=None):
+    """y[M,N] = act((x1 w1^T) * scale1 + (x2 w2^T) * scale2 + shift1 + shift2) -> bf16, ONE streaming launch: both
+    products are accumulated and scaled in fp32 (one bf16 rounding) — a bottleneck's conv3 + bn3 and its 1x1
+    stride-1 projection shortcut + BN, neither pre-BN tensor written.  ``relu_mask_out`` (uint8 [M * N / 8])
+    receives the ReLU bit mask of the stored output (bn.hip mode-3 layout).  Shapes outside ``stream_dual_ok``
+    raise (the launcher refuses them)."""
+    M, K1 = x1.shape
+    N = w1.shape[0]
+    K2 = x2.shape[1]
+    if not stream_dual_ok(N, K1, K2) or x2.shape[0] != M or w2.shape != (N, K2) or w1.shape[1] != K1:
+        raise ValueError("linear_dual_fwd: two [M, 64] x [N, 64]^T products with N % 128 == 0")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x1.device)
+    C().gemm(x1, w1, out, M, N, K1, KC, KC, x1.stride(0), w1.stride(0), out.stride(0), EPI_BF16, TILE_STREAM, K1, 1.0,
+             0.0, shift1, None, 0, ACT_RELU if relu else ACT_NONE, colscale=scale1, relu_mask_out=relu_mask_out, a2=x2,
+             b2=w2, lda2=x2.stride(0), ldb2=w2.stride(0), colscale2=scale2, bias2=shift2)
+    return out
+
+
 _SPLITK_WS = {}
 _SKINNY_FWD_TILES = 16  # 64x64 output tiles at or below which a long-K bf16 Linear forward splits K
 
