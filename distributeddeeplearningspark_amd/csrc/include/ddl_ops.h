@@ -291,6 +291,11 @@ int rnn_bwd(int cell, const float* dy, const float* U, const float* UT, const fl
 // y / dy rows are ldy floats wide and a direction owns columns [yoff, yoff + H): a Bidirectional concat output
 // is written (and its gradient read) in place.  yproc[d]: sequence rows of y / dy in processing order (a bare
 // go_backwards layer), else in input time order (Bidirectional).  dy is scaled by dscale on load (ave: 0.5).
+// mask (Keras Masking / Embedding(mask_zero)): step tm of row b is data iff mask[b T + tm] != 0.  A masked step
+// carries h (and c) over unchanged (so its output is the previous output, zeros before the first data step);
+// its saved "next" slots hold the carried state and its saved gates are never read for values.  Backward, its
+// gate pre-activation gradients are exactly zero and dh (dc) pass through.  A masked forward-only layer runs
+// as one direction with rev = 0.
 struct RnnDir {
   const float* xw[2];  // [B T][GH] projection (+ bias), or null: fused in-kernel from x / W / b (reg path, I <= 8)
   const float* W[2];
@@ -306,12 +311,19 @@ struct RnnDir {
   int rev[2], yoff[2], yproc[2];
   int ldy;
   float dscale;
+  const unsigned char* mask;  // [B][T] in memory time order, shared by the directions; null: every step is data
 };
 int rnn_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
                 int ract, hipStream_t s);
 int rnn_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract, hipStream_t s);
 // out = scale * (a + b), fp32 (Bidirectional sum / ave merge)
 int bidir_merge(const float* a, const float* b, float* out, long n, float scale, hipStream_t s);
+// Step masks [rows] (uint8, 1 = data).  From features x [rows][F] fp32: mask = any_f(x != mask_value); y (nullable)
+// = x * mask.  mask_apply: out [rows][F] = in * mask (the Masking gradient).  From token ids: mask = id != 0.
+int mask_from_features(const float* x, float* y, unsigned char* mask, long rows, int F, float mask_value,
+                       hipStream_t s);
+int mask_apply(const float* in, const unsigned char* mask, float* out, long rows, int F, hipStream_t s);
+int mask_from_ids(const long* ids, unsigned char* mask, long n, hipStream_t s);
 
 // ---------------- Keras layer element-wise ops (kernels/layer_ops.hip) ----------------
 // activation codes shared by the standalone Activation layer and the recurrent cells

@@ -17,6 +17,12 @@
 // time index t = rev ? T-1-s : s.  Saved tensors stay in memory time order; a reverse direction keeps the state
 // after step t in slot t (slot T = zero state), so the previous state is slot t + rev and the next one t + 1 - rev.
 // With DIR = false every direction value below is a compile-time constant and the code is the forward-only one.
+//
+// Masked instantiations (MASK = true, directed only; Keras Masking / Embedding(mask_zero)): RnnDir::mask is a uint8
+// [B][T] array in memory time order, read at t = time(s) and shared by the directions.  A masked step carries h (and
+// c) over in the element-wise state update and writes the carried state to the "next" slots and to y; backward it
+// emits zero gate gradients and hands dh (dc) on unchanged.  Contractions and barriers are those of MASK = false,
+// and with MASK = false no mask code is generated.
 #include <type_traits>
 
 #include "ddl_act.h"
@@ -79,11 +85,12 @@ __device__ __forceinline__ float hsig(float x) { return fminf(fmaxf(0.2f * x + 0
 __device__ __forceinline__ float hsig_d(float y) { return (y > 0.f && y < 1.f) ? 0.2f : 0.f; }
 
 // ----------------------------------------------------------------------------- forward
-template <int CELL, bool DIR = false>  // 0 = GRU (gates z, r, h), 1 = LSTM (gates i, f, c, o), 2 = SimpleRNN (h)
+template <int CELL, bool DIR = false, bool MASK = false>  // 0 = GRU (gates z, r, h), 1 = LSTM (gates i, f, c, o), 2 = SimpleRNN (h)
 __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ xw, const float* __restrict__ U,
                                                       float* __restrict__ hs, float* __restrict__ cs,
                                                       float* __restrict__ gates, float* __restrict__ y, int B, int T,
                                                       int H, int rs, int act, int ract, const DirArg<DIR> dr) {
+  static_assert(DIR || !MASK, "masked recurrences run as directed launches");
   constexpr int G = CELL == 0 ? 3 : (CELL == 1 ? 4 : 1);
   extern __shared__ float sm[];
   const int GH = G * H;
@@ -147,16 +154,20 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
     for (int i = threadIdx.x; i < nb * H; i += blockDim.x) {
       const int r = i / H, k = i - r * H;
       const float* g = gb + r * GH;
+      // A masked step carries the state over.  The mask selects the gate values (z = 1; i = 0, f = 1), not the
+      // result, so the arithmetic is the unmasked kernel's: 1 * h + 0 * hh is h exactly.
+      bool data = true;
+      if constexpr (MASK) data = dr.mask[(long)(b0 + r) * T + t] != 0;
       float hn;
       if (CELL == 2) {
-        hn = g[k];
+        hn = data ? g[k] : h[i];
       } else if (CELL == 0) {
-        const float z = g[k], hh = g[2 * H + k];
+        const float z = data ? g[k] : 1.f, hh = g[2 * H + k];
         hn = z * h[i] + (1.f - z) * hh;
       } else {
-        const float cn = g[H + k] * c[i] + g[k] * g[2 * H + k];
+        const float cn = (data ? g[H + k] : 1.f) * c[i] + (data ? g[k] : 0.f) * g[2 * H + k];
         c[i] = cn;
-        hn = g[3 * H + k] * act_f(act, cn);
+        hn = data ? g[3 * H + k] * act_f(act, cn) : h[i];
         cs[dz.next_slot((long)(b0 + r), T, t) * H + k] = cn;
       }
       h[i] = hn;
@@ -174,12 +185,13 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
 
 // ----------------------------------------------------------------------------- backward
 // UT = U^T [GH][H]; dgates [B][T][GH] = d(pre-activation)
-template <int CELL, bool DIR = false>
+template <int CELL, bool DIR = false, bool MASK = false>
 __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ UT,
                                                       const float* __restrict__ hs, const float* __restrict__ cs,
                                                       const float* __restrict__ gates, float* __restrict__ dgates,
                                                       int B, int T, int H, int rs, int act, int ract,
                                                       const DirArg<DIR> dr) {
+  static_assert(DIR || !MASK, "masked recurrences run as directed launches");
   constexpr int G = CELL == 0 ? 3 : (CELL == 1 ? 4 : 1);
   extern __shared__ float sm[];
   const int GH = G * H;
@@ -208,6 +220,14 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
       const float* g = gates + (row * T + t) * GH;
       const float hp = hs[dz.prev_slot(row, T, t) * H + k];
       float* p = dp + r * GH;
+      if constexpr (MASK) {
+        if (!dr.mask[row * T + t]) {  // masked step: zero gate gradients, dh (and dc, in aux) pass through
+          for (int q = 0; q < G; ++q) p[q * H + k] = 0.f;
+          dh[i] = d;  // this thread's own element: read again only by itself, in the last phase
+          if (CELL == 0) aux[i] = 0.f;
+          continue;
+        }
+      }
       if (CELL == 2) {
         p[k] = d * act_d(act, g[k]);
       } else if (CELL == 0) {
@@ -237,6 +257,9 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
         for (int j = 0; j < H; ++j) drh += p[2 * H + j] * UT[(long)(2 * H + j) * H + k];
         const float hp = hs[dz.prev_slot(row, T, t) * H + k];
         const float rg = gates[(row * T + t) * GH + H + k];
+        if constexpr (MASK) {
+          if (!dr.mask[row * T + t]) continue;  // dr stays the zero written above
+        }
         dp[r * GH + H + k] = drh * hp * act_d(ract, rg);
         aux[i] += drh * rg;
       }
@@ -248,6 +271,9 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
       const int r = i / H, k = i - r * H;
       const float* p = dp + r * GH;
       float s = CELL == 0 ? aux[i] : 0.f;
+      if constexpr (MASK) {
+        if (!dr.mask[(long)(b0 + r) * T + t]) s = dh[i];  // the carried dh; every p[j] of the row is zero
+      }
       for (int j = 0; j < jend; ++j) s += p[j] * UT[(long)j * H + k];
       dh[i] = s;
     }
@@ -313,13 +339,16 @@ constexpr int bwd_threads() { return H * (((CELL == 0 ? 3 : 4) * H / 64) <= 4 ? 
 // REP: replica-batched (RnnRep): the workgroup's replica is b0 / rp.B; W / U / bias come from its table
 // entries and x from its resident shard at mini-batch (*rp.ctr % rp.nbr[r]) — outputs stay global-row indexed.
 // DIR: directed (RnnDir): blockIdx.y is the direction; xw / W / bias / U / hs / cs / gates / y come from its table entry.
-template <int CELL, int H, int BB_, bool FUSE, bool REP = false, bool DIR = false>
+// MASK: masked steps (RnnDir::mask) carry the state over; the byte of the element this thread owns in the state
+// update is prefetched with the step's inputs.
+template <int CELL, int H, int BB_, bool FUSE, bool REP = false, bool DIR = false, bool MASK = false>
 __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     const float* __restrict__ xw, const float* __restrict__ x, const float* __restrict__ W,
     const float* __restrict__ bias, int I, const float* __restrict__ U, float* __restrict__ hs,
     float* __restrict__ cs, float* __restrict__ gates, float* __restrict__ y, int B, int T, int rs,
     const RegArg<DIR> rp) {
   static_assert(!(REP && DIR), "replica batching is forward-only");
+  static_assert(DIR || !MASK, "masked recurrences run as directed launches");
   constexpr int G = CELL == 0 ? 3 : 4;
   constexpr int GH = G * H;
   constexpr int KS = H / CH;
@@ -397,6 +426,14 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     hs[dz.zero_slot(erow, T) * H + ek] = 0.f;
     if (CELL == 1) cs[dz.zero_slot(erow, T) * H + ek] = 0.f;
   }
+  // mask byte of this thread's state element at step s: clamped and unconditional like fetch_x, and issued before
+  // the step's x loads, so the wait for those covers it
+  const long mrow = (b0 + min(er, nb - 1)) * (long)T;
+  auto fetch_m = [&](int s) -> unsigned {
+    if constexpr (MASK) return rp.mask[mrow + min(max(dz.time(s, T), 0), T - 1) + zoff];
+    else return 1u;
+  };
+  unsigned mcur = fetch_m(0);
   float xr[BB_][IMAX], xv[BB_];
   fetch_x(0, xr);
   proj(xr, xv);
@@ -420,6 +457,7 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
   };
   for (int s = 0; s < T; ++s) {
     const int t = dz.time(s, T);  // memory time index of processing step s
+    const unsigned mnext = fetch_m(s + 1);
     fetch_x(s + 1, xr);  // the next step's inputs (consumed at the end of this step)
     float acc[BB_];
     if (CELL == 1 || j < 2 * H) {  // wave-uniform: 2H columns span whole waves
@@ -452,15 +490,20 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     proj(xr, xnext);
 #pragma unroll
     for (int r = 0; r < BB_; ++r) asm volatile("" ::"v"(xnext[r]) : "memory");  // computed here, not sunk past the stores
+    if constexpr (MASK) asm volatile("" ::"v"(mnext) : "memory");
     if (eown) {
+      // A masked step carries the state over.  The mask selects the gate values (z = 1; i = 0, f = 1), not the
+      // result, so the arithmetic is the unmasked kernel's: 1 * h + 0 * hh is h exactly.
+      const bool data = !MASK || mcur != 0;
       float hn;
       if (CELL == 0) {
-        const float z = gb[er][ek], hh = gb[er][2 * H + ek];
+        const float z = data ? gb[er][ek] : 1.f, hh = gb[er][2 * H + ek];
         hn = z * h[er][cpos(ek)] + (1.f - z) * hh;
       } else {
-        const float cn = gb[er][H + ek] * c[er][cpos(ek)] + gb[er][ek] * gb[er][2 * H + ek];
+        const float cn = (data ? gb[er][H + ek] : 1.f) * c[er][cpos(ek)] +
+                         (data ? gb[er][ek] : 0.f) * gb[er][2 * H + ek];
         c[er][cpos(ek)] = cn;
-        hn = gb[er][3 * H + ek] * tanhf(cn);
+        hn = data ? gb[er][3 * H + ek] * tanhf(cn) : h[er][cpos(ek)];
         cs[dz.next_slot(erow, T, t) * H + ek] = cn;
       }
       h[er][cpos(ek)] = hn;
@@ -474,16 +517,20 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     }
 #pragma unroll
     for (int r = 0; r < BB_; ++r) xv[r] = xnext[r];
+    mcur = mnext;
     lds_barrier();
   }
 }
 
-template <int CELL, int H, int BB_, bool REP = false, bool DIR = false>
+// MASK: a masked step (RnnDir::mask, its byte prefetched with the step's saved activations) writes zero gate
+// gradients and hands dh on through the direct-part row (GRU: aux, LSTM: the otherwise unused hpl); dc stays in aux.
+template <int CELL, int H, int BB_, bool REP = false, bool DIR = false, bool MASK = false>
 __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
     const float* __restrict__ dy, const float* __restrict__ U, const float* __restrict__ hs,
     const float* __restrict__ cs, const float* __restrict__ gates, float* __restrict__ dgates, int B, int T, int rs,
     const RegArg<DIR> rp) {
   static_assert(!(REP && DIR), "replica batching is forward-only");
+  static_assert(DIR || !MASK, "masked recurrences run as directed launches");
   constexpr int G = CELL == 0 ? 3 : 4;
   constexpr int GH = G * H;
   constexpr int JS = GH / CH;                            // column chunks
@@ -514,15 +561,20 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
     u[i] = v.x; u[i + 1] = v.y; u[i + 2] = v.z; u[i + 3] = v.w;
   }
   for (int i = tid; i < BB_ * H; i += NT) (&dh[0][0])[i] = (&aux[0][0])[i] = 0.f;
+  if constexpr (MASK && CELL == 1) {  // rows past the batch are never written
+    for (int i = tid; i < BB_ * H; i += NT) (&hpl[0][0])[i] = 0.f;
+  }
   for (int i = tid; i < BB_ * JS * CP; i += NT) (&p[0][0])[i] = 0.f;
   // element owned in the element-wise phase, and its prefetched inputs
   const int er = tid / H, ek = tid - er * H;
   const bool eown = er < nb;
   const long erow = b0 + er;
   struct In { float d, g0, g1, g2, g3, hp, cn, cp; };
-  auto load_in = [&](int s, In& v) {
+  unsigned mcur = 1, mnxt = 1;  // mask bytes of the current and the prefetched step (MASK only)
+  auto load_in = [&](int s, In& v, unsigned& m) {
     if (!eown || s < 0) return;  // the guard is on the processing step; every index below is then in range
     const int t = dz.time(s, T);
+    if constexpr (MASK) m = rp.mask[erow * T + t];
     v.d = rs ? dz.dyv(dy[dz.yseq(erow, T, s, t, H, ek)]) : (s == T - 1 ? dz.dyv(dy[dz.ylast(erow, H, ek)]) : 0.f);
     const float* g = gates + (erow * T + t) * GH;
     v.g0 = g[ek]; v.g1 = g[H + ek]; v.g2 = g[2 * H + ek];
@@ -535,7 +587,7 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
     }
   };
   In cur{}, nxt{};
-  load_in(T - 1, cur);
+  load_in(T - 1, cur, mcur);
   retire_vm_loads();
   __syncthreads();
   auto contract = [&](bool use, float* acc) {
@@ -563,26 +615,28 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
   };
   for (int s = T - 1; s >= 0; --s) {
     const int t = dz.time(s, T);  // memory time index of processing step s
-    load_in(s - 1, nxt);  // prefetch the previous step's saved activations
+    load_in(s - 1, nxt, mnxt);  // prefetch the previous step's saved activations
     if (eown) {
       const float d = dh[er][ek] + cur.d;
+      const bool data = !MASK || mcur != 0;  // a masked step: zero gate gradients, dh (and dc) pass through
       float* pr = p[er];
       if (CELL == 0) {
         const float z = cur.g0, hh = cur.g2;
-        pr[cpos(ek)] = d * (cur.hp - hh) * hsig_d(z);
-        pr[cpos(2 * H + ek)] = d * (1.f - z) * (1.f - hh * hh);
-        aux[er][ek] = d * z;
+        pr[cpos(ek)] = data ? d * (cur.hp - hh) * hsig_d(z) : 0.f;
+        pr[cpos(2 * H + ek)] = data ? d * (1.f - z) * (1.f - hh * hh) : 0.f;
+        aux[er][ek] = data ? d * z : d;
         hpl[er][ek] = cur.hp;
         rgl[er][ek] = cur.g1;
       } else {
         const float gi = cur.g0, gf = cur.g1, gg = cur.g2, go = cur.g3;
         const float tc = tanhf(cur.cn);
         const float dc = aux[er][ek] + d * go * (1.f - tc * tc);
-        pr[cpos(ek)] = dc * gg * hsig_d(gi);
-        pr[cpos(H + ek)] = dc * cur.cp * hsig_d(gf);
-        pr[cpos(2 * H + ek)] = dc * gi * (1.f - gg * gg);
-        pr[cpos(3 * H + ek)] = d * tc * hsig_d(go);
-        aux[er][ek] = dc * gf;
+        pr[cpos(ek)] = data ? dc * gg * hsig_d(gi) : 0.f;
+        pr[cpos(H + ek)] = data ? dc * cur.cp * hsig_d(gf) : 0.f;
+        pr[cpos(2 * H + ek)] = data ? dc * gi * (1.f - gg * gg) : 0.f;
+        pr[cpos(3 * H + ek)] = data ? d * tc * hsig_d(go) : 0.f;
+        if (data) aux[er][ek] = dc * gf;  // a masked step leaves the running dc as it is
+        if constexpr (MASK) hpl[er][ek] = data ? 0.f : d;  // the carried dh, added in phase 1
       }
     }
     lds_barrier();
@@ -602,7 +656,7 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
           }
         } else {
 #pragma unroll
-          for (int r = 0; r < BB_; ++r) dh[r][k] = (CELL == 0 ? aux[r][k] : 0.f) + acc[r];
+          for (int r = 0; r < BB_; ++r) dh[r][k] = (CELL == 0 ? aux[r][k] : (MASK ? hpl[r][k] : 0.f)) + acc[r];
         }
       }
       if (ph == 0) lds_barrier();
@@ -612,6 +666,7 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
       dgates[((long)(b0 + r) * T + t) * GH + jj] = p[r][cpos(jj)];
     }
     cur = nxt;
+    if constexpr (MASK) mcur = mnxt;
     lds_barrier();
   }
 }
@@ -715,8 +770,8 @@ int launch_bwd_reg(const float* dy, const float* U, const float* hs, const float
   return (int)hipGetLastError();
 }
 
-// directed launches: grid.y = direction, everything per direction comes from the table
-template <int CELL, int H, int BB_>
+// directed launches: grid.y = direction, everything per direction comes from the table (MASK: d.mask is set)
+template <int CELL, int H, int BB_, bool MASK>
 int launch_fwd_reg_dir(const RnnDir& d, int ndir, const float* x, int I, int B, int T, int rs, hipStream_t s) {
   const bool fuse = !d.xw[0];
   if (fuse && (I < 1 || I > IMAX)) return (int)hipErrorInvalidValue;
@@ -724,26 +779,113 @@ int launch_fwd_reg_dir(const RnnDir& d, int ndir, const float* x, int I, int B, 
   const float* const np = nullptr;
   float* const nq = nullptr;
   if (fuse)
-    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, true, false, true>), grid, block, 0, s, np, x, np, np, I, np,
-                       nq, nq, nq, nq, B, T, rs, d);
+    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, true, false, true, MASK>), grid, block, 0, s, np, x, np, np,
+                       I, np, nq, nq, nq, nq, B, T, rs, d);
   else
-    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, false, false, true>), grid, block, 0, s, np, x, np, np, I, np,
-                       nq, nq, nq, nq, B, T, rs, d);
+    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, false, false, true, MASK>), grid, block, 0, s, np, x, np, np,
+                       I, np, nq, nq, nq, nq, B, T, rs, d);
   return (int)hipGetLastError();
 }
 
-template <int CELL, int H, int BB_>
+template <int CELL, int H, int BB_, bool MASK>
 int launch_bwd_reg_dir(const RnnDir& d, int ndir, int B, int T, int rs, hipStream_t s) {
   const dim3 grid((B + BB_ - 1) / BB_, ndir);
   const float* const np = nullptr;
-  hipLaunchKernelGGL((rnn_bwd_reg_kernel<CELL, H, BB_, false, true>), grid, dim3(bwd_threads<CELL, H>()), 0, s, np, np,
-                     np, np, np, (float*)nullptr, B, T, rs, d);
+  hipLaunchKernelGGL((rnn_bwd_reg_kernel<CELL, H, BB_, false, true, MASK>), grid, dim3(bwd_threads<CELL, H>()), 0, s,
+                     np, np, np, np, np, (float*)nullptr, B, T, rs, d);
+  return (int)hipGetLastError();
+}
+
+template <bool MASK>
+int launch_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
+                   int ract, hipStream_t s) {
+  const bool reg = rnn_reg_path(cell, H, act, ract);
+  if (reg && H == 128)
+    return cell == 0 ? launch_fwd_reg_dir<0, 128, RNN_BB_FWD, MASK>(d, ndir, x, I, B, T, rs, s)
+                     : launch_fwd_reg_dir<1, 128, RNN_BB_FWD, MASK>(d, ndir, x, I, B, T, rs, s);
+  if (reg && H == 64)
+    return cell == 0 ? launch_fwd_reg_dir<0, 64, 2, MASK>(d, ndir, x, I, B, T, rs, s)
+                     : launch_fwd_reg_dir<1, 64, 2, MASK>(d, ndir, x, I, B, T, rs, s);
+  if (!d.xw[0]) return (int)hipErrorInvalidValue;  // generic kernels need the projection precomputed
+  const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
+  const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
+  const int threads = std::min(512, ((G * H + 63) / 64) * 64);
+  const dim3 grid((B + BB - 1) / BB, ndir);
+  const float* const np = nullptr;
+  float* const nq = nullptr;
+  if (cell == 0)
+    hipLaunchKernelGGL((rnn_fwd_kernel<0, true, MASK>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H,
+                       rs, act, ract, d);
+  else if (cell == 1)
+    hipLaunchKernelGGL((rnn_fwd_kernel<1, true, MASK>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H,
+                       rs, act, ract, d);
+  else
+    hipLaunchKernelGGL((rnn_fwd_kernel<2, true, MASK>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H,
+                       rs, act, ract, d);
+  return (int)hipGetLastError();
+}
+
+template <bool MASK>
+int launch_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract,
+                   hipStream_t s) {
+  const bool reg = rnn_reg_path(cell, H, act, ract);
+  if (reg && H == 128)
+    return cell == 0 ? launch_bwd_reg_dir<0, 128, RNN_BB_BWD, MASK>(d, ndir, B, T, rs, s)
+                     : launch_bwd_reg_dir<1, 128, RNN_BB_BWD, MASK>(d, ndir, B, T, rs, s);
+  if (reg && H == 64)
+    return cell == 0 ? launch_bwd_reg_dir<0, 64, 2, MASK>(d, ndir, B, T, rs, s)
+                     : launch_bwd_reg_dir<1, 64, 2, MASK>(d, ndir, B, T, rs, s);
+  const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
+  const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
+  const int threads = std::min(512, ((G * H + 63) / 64) * 64);
+  const dim3 grid((B + BB - 1) / BB, ndir);
+  const float* const np = nullptr;
+  if (cell == 0)
+    hipLaunchKernelGGL((rnn_bwd_kernel<0, true, MASK>), grid, dim3(threads), lds, s, np, np, np, np, np,
+                       (float*)nullptr, B, T, H, rs, act, ract, d);
+  else if (cell == 1)
+    hipLaunchKernelGGL((rnn_bwd_kernel<1, true, MASK>), grid, dim3(threads), lds, s, np, np, np, np, np,
+                       (float*)nullptr, B, T, H, rs, act, ract, d);
+  else
+    hipLaunchKernelGGL((rnn_bwd_kernel<2, true, MASK>), grid, dim3(threads), lds, s, np, np, np, np, np,
+                       (float*)nullptr, B, T, H, rs, act, ract, d);
   return (int)hipGetLastError();
 }
 
 __global__ __launch_bounds__(256) void bidir_merge_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                           float* __restrict__ out, long n, float scale) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = scale * (a[i] + b[i]);
+}
+
+// Step masks (Keras Masking / Embedding(mask_zero)).  One wave per (b, t) row of x [rows][F]:
+// mask = any_f(x != mask_value); y (nullable) = x * mask.
+__global__ __launch_bounds__(256) void mask_from_features_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                 unsigned char* __restrict__ mask, long rows, int F,
+                                                                 float mask_value) {
+  const int lane = threadIdx.x & 63;
+  for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (long)gridDim.x * 4) {  // wave-uniform
+    const float* xr = x + row * F;
+    bool any = false;
+    for (int f = lane; f < F; f += 64) any |= xr[f] != mask_value;
+    const bool data = __any(any);
+    if (lane == 0) mask[row] = data ? 1 : 0;
+    if (y) {
+      for (int f = lane; f < F; f += 64) y[row * F + f] = data ? xr[f] : 0.f;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void mask_apply_kernel(const float* __restrict__ in,
+                                                         const unsigned char* __restrict__ mask,
+                                                         float* __restrict__ out, long rows, int F) {
+  const long n = rows * F;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+    out[i] = mask[i / F] ? in[i] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void mask_from_ids_kernel(const long* __restrict__ ids,
+                                                            unsigned char* __restrict__ mask, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) mask[i] = ids[i] != 0;
 }
 
 }  // namespace
@@ -834,62 +976,44 @@ int rnn_bwd(int cell, const float* dy, const float* U, const float* UT, const fl
 int rnn_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
                 int ract, hipStream_t s) {
   if (ndir < 1 || ndir > 2 || (ndir == 2 && !d.xw[0] != !d.xw[1])) return (int)hipErrorInvalidValue;
-  const bool reg = rnn_reg_path(cell, H, act, ract);
-  if (reg && H == 128)
-    return cell == 0 ? launch_fwd_reg_dir<0, 128, RNN_BB_FWD>(d, ndir, x, I, B, T, rs, s)
-                     : launch_fwd_reg_dir<1, 128, RNN_BB_FWD>(d, ndir, x, I, B, T, rs, s);
-  if (reg && H == 64)
-    return cell == 0 ? launch_fwd_reg_dir<0, 64, 2>(d, ndir, x, I, B, T, rs, s)
-                     : launch_fwd_reg_dir<1, 64, 2>(d, ndir, x, I, B, T, rs, s);
-  if (!d.xw[0]) return (int)hipErrorInvalidValue;  // generic kernels need the projection precomputed
-  const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
-  const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
-  const int threads = std::min(512, ((G * H + 63) / 64) * 64);
-  const dim3 grid((B + BB - 1) / BB, ndir);
-  const float* const np = nullptr;
-  float* const nq = nullptr;
-  if (cell == 0)
-    hipLaunchKernelGGL((rnn_fwd_kernel<0, true>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H, rs, act,
-                       ract, d);
-  else if (cell == 1)
-    hipLaunchKernelGGL((rnn_fwd_kernel<1, true>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H, rs, act,
-                       ract, d);
-  else
-    hipLaunchKernelGGL((rnn_fwd_kernel<2, true>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H, rs, act,
-                       ract, d);
-  return (int)hipGetLastError();
+  return d.mask ? launch_fwd_dir<true>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s)
+                : launch_fwd_dir<false>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s);
 }
 
 int rnn_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract, hipStream_t s) {
   if (ndir < 1 || ndir > 2) return (int)hipErrorInvalidValue;
-  const bool reg = rnn_reg_path(cell, H, act, ract);
-  if (reg && H == 128)
-    return cell == 0 ? launch_bwd_reg_dir<0, 128, RNN_BB_BWD>(d, ndir, B, T, rs, s)
-                     : launch_bwd_reg_dir<1, 128, RNN_BB_BWD>(d, ndir, B, T, rs, s);
-  if (reg && H == 64)
-    return cell == 0 ? launch_bwd_reg_dir<0, 64, 2>(d, ndir, B, T, rs, s)
-                     : launch_bwd_reg_dir<1, 64, 2>(d, ndir, B, T, rs, s);
-  const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
-  const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
-  const int threads = std::min(512, ((G * H + 63) / 64) * 64);
-  const dim3 grid((B + BB - 1) / BB, ndir);
-  const float* const np = nullptr;
-  if (cell == 0)
-    hipLaunchKernelGGL((rnn_bwd_kernel<0, true>), grid, dim3(threads), lds, s, np, np, np, np, np, (float*)nullptr, B, T,
-                       H, rs, act, ract, d);
-  else if (cell == 1)
-    hipLaunchKernelGGL((rnn_bwd_kernel<1, true>), grid, dim3(threads), lds, s, np, np, np, np, np, (float*)nullptr, B, T,
-                       H, rs, act, ract, d);
-  else
-    hipLaunchKernelGGL((rnn_bwd_kernel<2, true>), grid, dim3(threads), lds, s, np, np, np, np, np, (float*)nullptr, B, T,
-                       H, rs, act, ract, d);
-  return (int)hipGetLastError();
+  return d.mask ? launch_bwd_dir<true>(cell, d, ndir, B, T, H, rs, act, ract, s)
+                : launch_bwd_dir<false>(cell, d, ndir, B, T, H, rs, act, ract, s);
 }
 
 int bidir_merge(const float* a, const float* b, float* out, long n, float scale, hipStream_t s) {
   if (n <= 0) return 0;
   const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 1024);
   hipLaunchKernelGGL(bidir_merge_kernel, dim3(blocks), dim3(256), 0, s, a, b, out, n, scale);
+  return (int)hipGetLastError();
+}
+
+int mask_from_features(const float* x, float* y, unsigned char* mask, long rows, int F, float mask_value,
+                       hipStream_t s) {
+  if (rows <= 0) return 0;
+  if (F < 1) return (int)hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)std::min<long>((rows + 3) / 4, 4096);
+  hipLaunchKernelGGL(mask_from_features_kernel, dim3(blocks), dim3(256), 0, s, x, y, mask, rows, F, mask_value);
+  return (int)hipGetLastError();
+}
+
+int mask_apply(const float* in, const unsigned char* mask, float* out, long rows, int F, hipStream_t s) {
+  if (rows <= 0) return 0;
+  if (F < 1) return (int)hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)std::min<long>((rows * F + 255) / 256, 4096);
+  hipLaunchKernelGGL(mask_apply_kernel, dim3(blocks), dim3(256), 0, s, in, mask, out, rows, F);
+  return (int)hipGetLastError();
+}
+
+int mask_from_ids(const long* ids, unsigned char* mask, long n, hipStream_t s) {
+  if (n <= 0) return 0;
+  const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(mask_from_ids_kernel, dim3(blocks), dim3(256), 0, s, ids, mask, n);
   return (int)hipGetLastError();
 }
 

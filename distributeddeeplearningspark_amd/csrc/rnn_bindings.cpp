@@ -61,13 +61,24 @@ int merge_id(const std::string& m) {
   return m == "concat" ? 1 : (m == "sum" ? 2 : 3);
 }
 
+// the step mask of x [B,T,..] as the kernels read it (null when there is none)
+const unsigned char* mask_ptr(const c10::optional<at::Tensor>& mask, const at::Tensor& x, const char* who) {
+  if (!mask) return nullptr;
+  TORCH_CHECK(mask->scalar_type() == at::kByte && mask->dim() == 2 && mask->size(0) == x.size(0) &&
+                  mask->size(1) == x.size(1), who, ": mask must be uint8 [B, T]");
+  TORCH_CHECK(mask->is_contiguous() && mask->device() == x.device(), who,
+              ": mask must be contiguous and on the input's device");
+  return mask->data_ptr<unsigned char>();
+}
+
 py::tuple dir_fwd(int c, const at::Tensor& x, const std::vector<DirWeights>& w, const std::vector<int>& rev, bool rs,
-                  int merge, bool yproc, int64_t act, int64_t ract) {
+                  int merge, bool yproc, int64_t act, int64_t ract, const c10::optional<at::Tensor>& mask) {
   const int G = gates_of(c);
   const int nd = (int)w.size();
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
   const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = w[0].U.size(0);
   TORCH_CHECK(T >= 1, "rnn_fwd: empty sequence");
+  const unsigned char* mk = mask_ptr(mask, x, "rnn_fwd");
   at::DeviceGuard g(x.device());
   at::Tensor xc = x.contiguous();
   auto opt = x.options();
@@ -104,6 +115,7 @@ py::tuple dir_fwd(int c, const at::Tensor& x, const std::vector<DirWeights>& w, 
   }
   dr.ldy = (int)Hy;
   dr.dscale = 1.f;
+  dr.mask = mk;
   int e = rnn_fwd_dir(c, dr, nd, xc.data_ptr<float>(), (int)I, (int)B, (int)T, (int)H, rs ? 1 : 0, (int)act, (int)ract,
                       cur_stream());
   TORCH_CHECK(e == 0, "rnn_fwd launch failed: ", hipGetErrorString((hipError_t)e));
@@ -167,10 +179,13 @@ py::tuple dir_param_grads(int c, const at::Tensor& dg, const at::Tensor& hs, con
 // Returns (dx | None, [(dW, dU, db) per direction]) with None for what went into the given gradient buffers.
 py::tuple dir_bwd(int c, const at::Tensor& dy, const at::Tensor& x, const std::vector<DirWeights>& w,
                   const std::vector<int>& rev, bool rs, int merge, bool yproc, const std::vector<at::Tensor>& saved,
-                  const std::vector<DirWeights>& gr, bool need_dx, int64_t act, int64_t ract) {
+                  const std::vector<DirWeights>& gr, bool need_dx, int64_t act, int64_t ract,
+                  const c10::optional<at::Tensor>& mask) {
   const int G = gates_of(c);
   const int nd = (int)w.size();
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3, "rnn_bwd: x [B,T,I] on GPU");
   const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = w[0].U.size(0);
+  const unsigned char* mk = mask_ptr(mask, x, "rnn_bwd");
   const bool reg = rnn_reg_path(c, (int)H, (int)act, (int)ract);
   TORCH_CHECK(saved.size() == 3, "rnn_bwd: saved = [hs, cs, gates]");
   const at::Tensor& hs = saved[0];
@@ -208,6 +223,7 @@ py::tuple dir_bwd(int c, const at::Tensor& dy, const at::Tensor& x, const std::v
   }
   dr.ldy = (int)Hy;
   dr.dscale = merge == 3 ? 0.5f : 1.f;
+  dr.mask = mk;
   const int e = rnn_bwd_dir(c, dr, nd, (int)B, (int)T, (int)H, rs ? 1 : 0, (int)act, (int)ract, cur_stream());
   TORCH_CHECK(e == 0, "rnn_bwd launch failed: ", hipGetErrorString((hipError_t)e));
   py::object dx = py::none();
@@ -226,36 +242,42 @@ py::tuple dir_bwd(int c, const at::Tensor& dy, const at::Tensor& x, const std::v
 at::Tensor opt_tensor(const py::handle& o) { return o.is_none() ? at::Tensor() : o.cast<at::Tensor>(); }
 
 py::tuple birnn_fwd_(const std::string& cell, const at::Tensor& x, py::list Ws, py::list Us, py::list bs, bool rs,
-                     const std::string& merge, int64_t act, int64_t ract) {
+                     const std::string& merge, int64_t act, int64_t ract, c10::optional<at::Tensor> mask) {
   const int c = cell_id(cell);
   TORCH_CHECK(Ws.size() == 2, "birnn_fwd: [forward, backward] weights");
-  return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), gates_of(c)), {0, 1}, rs, merge_id(merge), false, act, ract);
+  return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), gates_of(c)), {0, 1}, rs, merge_id(merge), false, act, ract,
+                 mask);
 }
 
 py::tuple birnn_bwd_(const std::string& cell, const at::Tensor& dy, const at::Tensor& x, py::list Ws, py::list Us,
                      py::list bs, bool rs, const std::string& merge, std::vector<at::Tensor> saved, py::list gWs,
-                     py::list gUs, py::list gbs, bool need_dx, int64_t act, int64_t ract) {
+                     py::list gUs, py::list gbs, bool need_dx, int64_t act, int64_t ract,
+                     c10::optional<at::Tensor> mask) {
   const int c = cell_id(cell);
   TORCH_CHECK(Ws.size() == 2 && gWs.size() == 2 && gUs.size() == 2 && gbs.size() == 2,
               "birnn_bwd: [forward, backward] weights and gradient buffers");
   std::vector<DirWeights> gr(2);
   for (int d = 0; d < 2; ++d) gr[d] = {opt_tensor(gWs[d]), opt_tensor(gUs[d]), opt_tensor(gbs[d])};
   return dir_bwd(c, dy, x, dir_weights(Ws, Us, bs, x.size(2), gates_of(c)), {0, 1}, rs, merge_id(merge), false, saved,
-                 gr, need_dx, act, ract);
+                 gr, need_dx, act, ract, mask);
 }
 
 // reverse: the sequence is processed last-to-first (go_backwards).  y_input_order: a returned sequence (and its
 // gradient) is in input time order; default is Keras' processing order.  Both default to the forward layer.
+// mask: uint8 [B, T] step mask (1 = data); a masked layer runs the directed kernels, forward as one direction.
 py::tuple rnn_fwd_(const std::string& cell, const at::Tensor& x, const at::Tensor& W, const at::Tensor& U,
-                   c10::optional<at::Tensor> b, bool rs, int64_t act, int64_t ract, bool reverse, bool y_input_order) {
+                   c10::optional<at::Tensor> b, bool rs, int64_t act, int64_t ract, bool reverse, bool y_input_order,
+                   c10::optional<at::Tensor> mask) {
   const int c = cell_id(cell);
   const int G = gates_of(c);
-  if (reverse) {
+  if (reverse || mask) {
+    TORCH_CHECK(x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
     py::list Ws, Us, bs;
     Ws.append(W);
     Us.append(U);
     bs.append(b ? py::cast(*b) : py::none());
-    return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), G), {1}, rs, 0, !y_input_order, act, ract);
+    return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), G), {reverse ? 1 : 0}, rs, 0, !y_input_order, act, ract,
+                   mask);
   }
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
   const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = U.size(0);
@@ -294,18 +316,20 @@ py::tuple rnn_fwd_(const std::string& cell, const at::Tensor& x, const at::Tenso
 py::tuple rnn_bwd_(const std::string& cell, const at::Tensor& dy, const at::Tensor& x, const at::Tensor& W,
                    const at::Tensor& U, c10::optional<at::Tensor> b, bool rs, std::vector<at::Tensor> saved,
                    c10::optional<at::Tensor> gW, c10::optional<at::Tensor> gU, c10::optional<at::Tensor> gb,
-                   bool need_dx, int64_t act, int64_t ract, bool reverse, bool y_input_order) {
+                   bool need_dx, int64_t act, int64_t ract, bool reverse, bool y_input_order,
+                   c10::optional<at::Tensor> mask) {
   const int c = cell_id(cell);
   const int G = gates_of(c);
-  if (reverse) {
+  if (reverse || mask) {
+    TORCH_CHECK(x.dim() == 3, "rnn_bwd: x [B,T,I] fp32 on GPU");
     py::list Ws, Us, bs;
     Ws.append(W);
     Us.append(U);
     bs.append(b ? py::cast(*b) : py::none());
     std::vector<DirWeights> gr(1);
     gr[0] = {gW ? *gW : at::Tensor(), gU ? *gU : at::Tensor(), gb ? *gb : at::Tensor()};
-    py::tuple r = dir_bwd(c, dy, x, dir_weights(Ws, Us, bs, x.size(2), G), {1}, rs, 0, !y_input_order, saved, gr,
-                          need_dx, act, ract);
+    py::tuple r = dir_bwd(c, dy, x, dir_weights(Ws, Us, bs, x.size(2), G), {reverse ? 1 : 0}, rs, 0, !y_input_order,
+                          saved, gr, need_dx, act, ract, mask);
     py::tuple pg = r[1].cast<py::list>()[0].cast<py::tuple>();
     return py::make_tuple(r[0], pg[0], pg[1], pg[2]);
   }
@@ -464,25 +488,67 @@ void rnn_replica_step_(const std::string& cell, py::list xs, py::list ys, py::li
   TORCH_CHECK(e == 0, "rnn_replica_step launch failed: ", hipGetErrorString((hipError_t)e));
 }
 
+// Step masks (kernels/rnn.hip): returns (y, mask); y is x itself unless apply (mask_value != 0 zeroes masked steps)
+py::tuple mask_from_features_(const at::Tensor& x, double mask_value, bool apply) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3 && x.is_contiguous(),
+              "mask_from_features: x [B,T,F] contiguous fp32 on GPU");
+  at::DeviceGuard g(x.device());
+  at::Tensor mask = at::empty({x.size(0), x.size(1)}, x.options().dtype(at::kByte));
+  at::Tensor y = apply ? at::empty_like(x) : x;
+  const int e = mask_from_features(x.data_ptr<float>(), apply ? y.data_ptr<float>() : nullptr,
+                                   mask.data_ptr<unsigned char>(), x.size(0) * x.size(1), (int)x.size(2),
+                                   (float)mask_value, cur_stream());
+  TORCH_CHECK(e == 0, "mask_from_features launch failed: ", hipGetErrorString((hipError_t)e));
+  return py::make_tuple(y, mask);
+}
+
+at::Tensor mask_apply_(const at::Tensor& x, const at::Tensor& mask) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3 && x.is_contiguous(),
+              "mask_apply: x [B,T,F] contiguous fp32 on GPU");
+  mask_ptr(mask, x, "mask_apply");
+  at::DeviceGuard g(x.device());
+  at::Tensor out = at::empty_like(x);
+  const int e = mask_apply(x.data_ptr<float>(), mask.data_ptr<unsigned char>(), out.data_ptr<float>(),
+                           x.size(0) * x.size(1), (int)x.size(2), cur_stream());
+  TORCH_CHECK(e == 0, "mask_apply launch failed: ", hipGetErrorString((hipError_t)e));
+  return out;
+}
+
+at::Tensor mask_from_ids_(const at::Tensor& ids) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.dim() == 2 && ids.is_contiguous(),
+              "mask_from_ids: ids [B,T] contiguous int64 on GPU");
+  at::DeviceGuard g(ids.device());
+  at::Tensor mask = at::empty(ids.sizes(), ids.options().dtype(at::kByte));
+  const int e = mask_from_ids(ids.data_ptr<int64_t>(), mask.data_ptr<unsigned char>(), ids.numel(), cur_stream());
+  TORCH_CHECK(e == 0, "mask_from_ids launch failed: ", hipGetErrorString((hipError_t)e));
+  return mask;
+}
+
 }  // namespace
 
 void register_rnn(py::module& m) {
   m.def("rnn_fwd", &rnn_fwd_, "persistent GRU/LSTM/SimpleRNN forward (fp32)", py::arg("cell"), py::arg("x"),
         py::arg("W"), py::arg("U"), py::arg("b"), py::arg("rs"), py::arg("act") = (int64_t)ACT_C_TANH,
-        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID, py::arg("reverse") = false, py::arg("y_input_order") = false);
+        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID, py::arg("reverse") = false, py::arg("y_input_order") = false,
+        py::arg("mask") = py::none());
   m.def("rnn_bwd", &rnn_bwd_, "persistent GRU/LSTM backward (fp32)", py::arg("cell"), py::arg("dy"), py::arg("x"),
         py::arg("W"), py::arg("U"), py::arg("b"), py::arg("rs"), py::arg("saved"), py::arg("gW") = py::none(),
         py::arg("gU") = py::none(), py::arg("gb") = py::none(), py::arg("need_dx") = true,
         py::arg("act") = (int64_t)ACT_C_TANH, py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID,
-        py::arg("reverse") = false, py::arg("y_input_order") = false);
+        py::arg("reverse") = false, py::arg("y_input_order") = false, py::arg("mask") = py::none());
   m.def("birnn_fwd", &birnn_fwd_, "Bidirectional GRU/LSTM/SimpleRNN forward: both directions in one recurrence launch",
         py::arg("cell"), py::arg("x"), py::arg("Ws"), py::arg("Us"), py::arg("bs"), py::arg("rs"),
         py::arg("merge") = "concat", py::arg("act") = (int64_t)ACT_C_TANH,
-        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID);
+        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID, py::arg("mask") = py::none());
   m.def("birnn_bwd", &birnn_bwd_, "Bidirectional backward: one recurrence launch, parameter gradients per direction",
         py::arg("cell"), py::arg("dy"), py::arg("x"), py::arg("Ws"), py::arg("Us"), py::arg("bs"), py::arg("rs"),
         py::arg("merge"), py::arg("saved"), py::arg("gWs"), py::arg("gUs"), py::arg("gbs"), py::arg("need_dx") = true,
-        py::arg("act") = (int64_t)ACT_C_TANH, py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID);
+        py::arg("act") = (int64_t)ACT_C_TANH, py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID,
+        py::arg("mask") = py::none());
+  m.def("mask_from_features", &mask_from_features_, "step mask any_f(x != mask_value) of x [B,T,F]; y = x * mask",
+        py::arg("x"), py::arg("mask_value"), py::arg("apply"));
+  m.def("mask_apply", &mask_apply_, "out = in * mask[..., None] (the Masking gradient)", py::arg("x"), py::arg("mask"));
+  m.def("mask_from_ids", &mask_from_ids_, "step mask ids != 0 of int64 token ids [B,T]", py::arg("ids"));
   m.def("rnn_replica_step", &rnn_replica_step_, "one training step of R co-located RNN -> Dense / MSE replicas");
   m.def("rnn_replica_ok", [](const std::string& cell, int64_t H, int64_t I, int64_t K, int64_t B) {
     return rnn_replica_ok(cell_id(cell), (int)H, (int)I, (int)K, (int)B);

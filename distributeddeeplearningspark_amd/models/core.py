@@ -50,6 +50,13 @@ class Layer:
     """Base layer.  Subclasses define ``build`` (create params with ``add_weight``),
     ``call`` and ``compute_output_shape``; shapes exclude the batch dimension."""
 
+    # Step masks of padded sequences (Keras Masking / Embedding(mask_zero)), known statically from the layer types:
+    # a producer's call(return_mask=True) returns (y, mask); a taker's call accepts mask= and hands the mask on
+    # when it returns sequences; a passer leaves the time axis alone.  Any other layer refuses a mask.
+    produces_mask = False
+    takes_mask = False
+    passes_mask = False
+
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
         _LAYER_TYPES[cls.__name__] = cls
@@ -198,6 +205,8 @@ _LOSS_ALIASES = {
 
 class Model(Layer):
     """A trainable network: owns the parameter arena, optimizer and loss."""
+
+    _masked = False  # True once Sequential.build_model() finds a layer that produces a step mask
 
     def __init__(self, name=None, **kw):
         super().__init__(name=name, **kw)
@@ -545,7 +554,27 @@ class Sequential(Model):
         for l in self.layers:
             shape = l.ensure_built(shape)
         self.output_shape = tuple(shape)
+        self._masked = self._check_mask_flow()
         self.built = True
+
+    def _check_mask_flow(self) -> bool:
+        """Static mask propagation: True when some layer produces a step mask.  A mask may only reach layers that
+        pass it on or consume it, and must be consumed (a recurrent layer returning its last state) before the
+        output: Keras would weight the loss per time step there, which this loss layer does not do."""
+        carried, any_mask = None, False  # the producer of the mask in flight
+        for l in self.layers:
+            if carried is not None and not (l.takes_mask or l.passes_mask):
+                raise ValueError(f"{type(l).__name__} layer {l.name!r} cannot receive the step mask produced by "
+                                 f"{carried.name!r}: only Dropout, Activation, Dense, recurrent and Bidirectional "
+                                 "layers take one")
+            if l.produces_mask:
+                carried, any_mask = l, True
+            elif carried is not None and l.takes_mask and not l.return_sequences:
+                carried = None
+        if carried is not None:
+            raise ValueError(f"the step mask produced by {carried.name!r} reaches the model output: masked losses are "
+                             "not supported (end the masked part with a recurrent layer that returns its last state)")
+        return any_mask
 
     def ends_with_softmax(self) -> bool:
         last = self.layers[-1] if self.layers else None
@@ -560,6 +589,8 @@ class Sequential(Model):
         from ..ops.norm import new_stats_workspace
         from .layers import Activation, BatchNormalization, Conv2D, Dense, MaxPooling2D
 
+        if self._masked:
+            return self._forward_masked(x, training, logits)
         L = self.layers
         n = len(L)
         i = 0
@@ -608,6 +639,29 @@ class Sequential(Model):
                 continue
             x = l.call(x, training)
             i += 1
+        return x
+
+    def _forward_masked(self, x, training, logits):
+        """``forward`` of a model with a step-mask producer (``_check_mask_flow``): layer by layer, the mask
+        handed from its producer to the recurrent layers behind it.  None of ``forward``'s graph-level fusions
+        is applied, in front of the mask producer or behind its consumer either: a ``Dense`` ->
+        ``Activation('relu')`` head of a masked model runs as two launches (same numbers), and only the final
+        softmax is still skipped for the fused loss."""
+        mask = None
+        last = self.layers[-1]
+        for l in self.layers:
+            if logits and l is last and getattr(l, "activation_name", None) == "softmax":
+                if hasattr(l, "supports_skip"):
+                    x = l.call(x, training, skip_activation=True)
+                break
+            if l.produces_mask:
+                x, mask = l.call(x, training, return_mask=True)
+            elif mask is not None and l.takes_mask:
+                x = l.call(x, training, mask=mask)
+                if not l.return_sequences:
+                    mask = None
+            else:
+                x = l.call(x, training)
         return x
 
     def _convbn_unit(self, conv, bn, x):

@@ -52,6 +52,8 @@ def _r8(n: int) -> int:
 
 
 class Activation(Layer):
+    passes_mask = True
+
     def __init__(self, activation, **kw):
         super().__init__(**kw)
         self.activation_name = _act_name(activation)
@@ -66,6 +68,8 @@ class Activation(Layer):
 
 
 class Dense(Layer):
+    passes_mask = True
+
     def __init__(self, units, activation=None, use_bias=True, kernel_initializer="glorot_uniform", **kw):
         super().__init__(**kw)
         self.units = int(units)
@@ -254,6 +258,8 @@ class Reshape(Layer):
 
 
 class Dropout(Layer):
+    passes_mask = True
+
     def __init__(self, rate, **kw):
         super().__init__(**kw)
         self.rate = float(rate)
@@ -301,10 +307,37 @@ class BatchNormalization(Layer):
                 "scale": self.scale}
 
 
+class Masking(Layer):
+    """Keras ``Masking``: a step ``[b, t]`` whose features all equal ``mask_value`` is masked.  The output is
+    ``x * mask`` and the step mask travels on to the recurrent layer behind (``Sequential.forward``), which
+    skips the masked steps."""
+
+    def __init__(self, mask_value=0.0, **kw):
+        super().__init__(**kw)
+        self.mask_value = float(mask_value)
+
+    produces_mask = True
+
+    def call(self, x, training=False, return_mask=False):
+        from ..ops import mask as mask_ops
+
+        y, mask = mask_ops.masking(x, self.mask_value)
+        return (y, mask) if return_mask else y
+
+    def get_config(self):
+        return {**super().get_config(), "mask_value": self.mask_value}
+
+
 class Embedding(Layer):
-    def __init__(self, input_dim, output_dim, **kw):
+    def __init__(self, input_dim, output_dim, mask_zero=False, **kw):
         super().__init__(**kw)
         self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+        # Keras: id 0 is padding and masked downstream; the table keeps input_dim rows (row 0 is never data)
+        self.mask_zero = bool(mask_zero)
+
+    @property
+    def produces_mask(self):
+        return self.mask_zero
 
     def build(self, s):
         self.embeddings = self.add_weight("embeddings", (self.input_dim, self.output_dim), P.uniform(0.05))
@@ -312,18 +345,25 @@ class Embedding(Layer):
     def compute_output_shape(self, s):
         return (*s, self.output_dim)
 
-    def call(self, x, training=False):
+    def call(self, x, training=False, return_mask=False):
         from ..ops import embedding as E
 
-        return E.embedding(x, self.embeddings.data, grad_w=self.embeddings.grad, on_grad=self.grad_hook)
+        y = E.embedding(x, self.embeddings.data, grad_w=self.embeddings.grad, on_grad=self.grad_hook)
+        if not return_mask:
+            return y
+        from ..ops import mask as mask_ops
+
+        return y, (mask_ops.ids_mask(x) if self.mask_zero else None)
 
     def get_config(self):
-        return {**super().get_config(), "input_dim": self.input_dim, "output_dim": self.output_dim}
+        return {**super().get_config(), "input_dim": self.input_dim, "output_dim": self.output_dim,
+                "mask_zero": self.mask_zero}
 
 
 class _Recurrent(Layer):
     n_gates = 1
     cell = "rnn"
+    takes_mask = True  # skips masked steps; passes the mask on with return_sequences, else consumes it
 
     def __init__(self, units, activation="tanh", recurrent_activation="hard_sigmoid", return_sequences=False,
                  use_bias=True, unit_forget_bias=True, go_backwards=False, **kw):
@@ -364,12 +404,13 @@ class _Recurrent(Layer):
     def compute_output_shape(self, s):
         return (s[0], self.units) if self.return_sequences else (self.units,)
 
-    def call(self, x, training=False):
+    def call(self, x, training=False, mask=None):
         return rnn_ops.recurrent(
             self.cell, x, self.kernel.data, self.recurrent_kernel.data, None if self.bias is None else self.bias.data,
             grads=(self.kernel.grad, self.recurrent_kernel.grad, None if self.bias is None else self.bias.grad),
             return_sequences=self.return_sequences, activation=self.activation,
-            recurrent_activation=self.recurrent_activation, on_grad=self.grad_hook, go_backwards=self.go_backwards)
+            recurrent_activation=self.recurrent_activation, on_grad=self.grad_hook, go_backwards=self.go_backwards,
+            mask=mask)
 
     def get_config(self):
         return {**super().get_config(), "units": self.units, "activation": self.activation,
@@ -406,6 +447,8 @@ class Bidirectional(Layer):
     Weights (Keras order): forward kernel, recurrent kernel, bias, then the backward layer's; parameter
     names ``<wrapper>/forward_<layer>/...`` and ``<wrapper>/backward_<layer>/...``."""
 
+    takes_mask = True  # both directions read the same mask
+
     def __init__(self, layer, merge_mode="concat", **kw):
         if isinstance(layer, dict):  # a Keras config ({"class_name", "config"})
             from .core import layer_from_config
@@ -435,6 +478,10 @@ class Bidirectional(Layer):
         for l in self.sublayers():
             l.ensure_built(s)
 
+    @property
+    def return_sequences(self):
+        return self.forward_layer.return_sequences
+
     def compute_output_shape(self, s):
         out = tuple(self.forward_layer.compute_output_shape(s))
         return (*out[:-1], 2 * out[-1]) if self.merge_mode == "concat" else out
@@ -444,12 +491,12 @@ class Bidirectional(Layer):
             if l.grad_hook is not None:
                 l.grad_hook()
 
-    def call(self, x, training=False):
+    def call(self, x, training=False, mask=None):
         f, b = self.forward_layer, self.backward_layer
         if f.go_backwards:
             # a wrapped go_backwards layer (rare): Keras then returns both sequences in reversed time order;
             # composed from the two single-direction ops
-            yf, yb = f.call(x, training), b.call(x, training)
+            yf, yb = f.call(x, training, mask=mask), b.call(x, training, mask=mask)
             if f.return_sequences:
                 yb = yb.flip(1)
             if self.merge_mode == "concat":
@@ -459,7 +506,7 @@ class Bidirectional(Layer):
         grads = lambda l: (l.kernel.grad, l.recurrent_kernel.grad, None if l.bias is None else l.bias.grad)
         y = rnn_ops.bidirectional(f.cell, x, wts(f), wts(b), grads=(grads(f), grads(b)), merge_mode=self.merge_mode,
                                   return_sequences=f.return_sequences, activation=f.activation,
-                                  recurrent_activation=f.recurrent_activation, on_grad=self._fire_hooks)
+                                  recurrent_activation=f.recurrent_activation, on_grad=self._fire_hooks, mask=mask)
         return y
 
     def get_config(self):

@@ -5,6 +5,8 @@
 * ``gru_regressor``   GRU(128, input (25,1)) + Dense(1) (``ddl_nyiso_aztk.py:201-203``), 50,049.
 * ``lstm_regressor``  LSTM(128) + Dense(1) (``ddl_nyiso_aztk.py:249-251``), 66,689.
 * ``bigru_regressor`` / ``bilstm_regressor``  the same regressors with a ``Bidirectional`` (concat) recurrent layer.
+* ``text_lstm_classifier``  Embedding(mask_zero) -> LSTM -> Dense(1, sigmoid) over zero-padded token ids
+                      (``utils.pad_sequences``); ``masked_gru_regressor``  Masking -> GRU -> Dense over padded series.
 * ``lenet5``          LeNet-5 on MNIST shape (BASELINE.json config #1).
 * ``vgg16``           VGG-16 (BN) in the CIFAR shape (BASELINE.json config #4).
 * ResNet-50 lives in ``resnet.py``; BERT-base in ``bert.py``.
@@ -12,8 +14,8 @@
 from __future__ import annotations
 
 from .core import Sequential
-from .layers import (GRU, LSTM, Activation, BatchNormalization, Bidirectional, Conv2D, Dense, Dropout, Flatten,
-                     MaxPooling2D)
+from .layers import (GRU, LSTM, Activation, BatchNormalization, Bidirectional, Conv2D, Dense, Dropout, Embedding,
+                     Flatten, Masking, MaxPooling2D)
 
 
 def mnist_cnn(nb_classes: int = 10, input_shape=(28, 28, 1), nb_filters: int = 32) -> Sequential:
@@ -55,6 +57,25 @@ def bigru_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outp
 def bilstm_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outputs: int = 1) -> Sequential:
     m = Sequential()
     m.add(Bidirectional(LSTM(units), input_shape=(seq_len, features)))
+    m.add(Dense(outputs, activation="linear"))
+    return m
+
+
+def text_lstm_classifier(vocab_size: int, maxlen: int, embed_dim: int = 32, units: int = 64) -> Sequential:
+    """The classic Keras text model over zero-padded id sequences: id 0 is padding and its steps are skipped."""
+    m = Sequential()
+    m.add(Embedding(vocab_size, embed_dim, mask_zero=True, input_shape=(maxlen,)))
+    m.add(LSTM(units))
+    m.add(Dense(1, activation="sigmoid"))
+    return m
+
+
+def masked_gru_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outputs: int = 1,
+                         mask_value: float = 0.0) -> Sequential:
+    """``gru_regressor`` over ragged series padded with ``mask_value`` to ``seq_len`` steps."""
+    m = Sequential()
+    m.add(Masking(mask_value=mask_value, input_shape=(seq_len, features)))
+    m.add(GRU(units))
     m.add(Dense(outputs, activation="linear"))
     return m
 

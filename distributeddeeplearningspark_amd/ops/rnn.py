@@ -17,6 +17,11 @@ into the arena in one launch.
 processing order) and ``bidirectional`` (both directions as ONE autograd node: one recurrence
 launch per pass with the direction on ``blockIdx.y``, the concat output written in place) run
 the directed instantiations of the same kernels; nothing is flipped or concatenated in memory.
+
+``mask`` (``uint8 [B, T]`` in input time order, 1 = data; ``ops/mask.py``): a masked step carries the state over,
+so its output is the previous output in processing order (zeros before the first data step) and the last
+output is the state after the last data step; its gate gradients are zero and dh / dc pass through.  Masked
+layers run the masked instantiations of the directed kernels; the mask is saved for the backward pass.
 """
 from __future__ import annotations
 
@@ -35,9 +40,11 @@ def _act(name):
 
 
 def recurrent_ref(cell, x, W, U, b, return_sequences, activation="tanh", recurrent_activation="hard_sigmoid",
-                  go_backwards=False):
+                  go_backwards=False, mask=None):
+    keep = None if mask is None else mask.to(torch.bool).unsqueeze(-1)  # [B, T, 1]
     if go_backwards:  # Keras: reversed input; a returned sequence stays in processing order
         x = x.flip(1)
+        keep = None if keep is None else keep.flip(1)
     B, T, _ = x.shape
     H = U.shape[0]
     act, ract = _act(activation), _act(recurrent_activation)
@@ -49,6 +56,7 @@ def recurrent_ref(cell, x, W, U, b, return_sequences, activation="tanh", recurre
     outs = []
     for t in range(T):
         xt = xw[:, t]
+        hp, cp = h, c
         if cell == "gru":
             hu = h @ U[:, : 2 * H]
             z = ract(xt[:, :H] + hu[:, :H])
@@ -65,16 +73,21 @@ def recurrent_ref(cell, x, W, U, b, return_sequences, activation="tanh", recurre
             h = o * act(c)
         else:
             h = act(xt + h @ U)
+        if keep is not None:  # a masked step carries the state (and so the output) over
+            h = torch.where(keep[:, t], h, hp)
+            c = torch.where(keep[:, t], c, cp)
         if return_sequences:
             outs.append(h)
     return torch.stack(outs, 1) if return_sequences else h
 
 
 def bidirectional_ref(cell, x, fwd, bwd, return_sequences, merge_mode="concat", activation="tanh",
-                      recurrent_activation="hard_sigmoid"):
-    """Both directions through ``recurrent_ref``; the backward sequence is re-reversed before the merge."""
-    yf = recurrent_ref(cell, x, *fwd, return_sequences, activation, recurrent_activation)
-    yb = recurrent_ref(cell, x, *bwd, return_sequences, activation, recurrent_activation, go_backwards=True)
+                      recurrent_activation="hard_sigmoid", mask=None):
+    """Both directions through ``recurrent_ref`` (the same mask to both); the backward sequence is re-reversed
+    before the merge."""
+    yf = recurrent_ref(cell, x, *fwd, return_sequences, activation, recurrent_activation, mask=mask)
+    yb = recurrent_ref(cell, x, *bwd, return_sequences, activation, recurrent_activation, go_backwards=True,
+                       mask=mask)
     if return_sequences:
         yb = yb.flip(1)
     if merge_mode == "concat":
@@ -93,54 +106,69 @@ def _act_codes(act, ract):
 
 class _RecurrentFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, W, U, b, gW, gU, gb, cfg):
+    def forward(ctx, x, W, U, b, gW, gU, gb, cfg, mask=None):
         cell, rs, act, ract, hook, rev = cfg
         ctx.cfg = cfg
+        ctx.masked = mask is not None
+        keep = () if mask is None else (mask,)  # saved for the backward, not recomputed
         dt = x.dtype
         xf, Wf, Uf = x.float(), W.float(), U.float()
         bf = None if b is None else b.float()
         if use_native(x):
             ctx.codes = _act_codes(act, ract)
-            y, saved = C().rnn_fwd(cell, xf.contiguous(), Wf.contiguous(), Uf.contiguous(), bf, rs, *ctx.codes, rev)
+            if mask is None:
+                y, saved = C().rnn_fwd(cell, xf.contiguous(), Wf.contiguous(), Uf.contiguous(), bf, rs, *ctx.codes, rev)
+            else:
+                y, saved = C().rnn_fwd(cell, xf.contiguous(), Wf.contiguous(), Uf.contiguous(), bf, rs, *ctx.codes, rev,
+                                       False, mask)
             ctx.native = True
             ctx.grads = (gW, gU, gb)
             ctx.needs_dx = ctx.needs_input_grad[0]
-            ctx.save_for_backward(xf, Wf, Uf, bf, *saved)
+            ctx.save_for_backward(xf, Wf, Uf, bf, *keep, *saved)
             return y.to(dt)
         ctx.native = False
         with torch.no_grad():
-            y = recurrent_ref(cell, xf, Wf, Uf, bf, rs, act, ract, rev)
+            y = recurrent_ref(cell, xf, Wf, Uf, bf, rs, act, ract, rev, mask)
         ctx.grads = (gW, gU, gb)
-        ctx.save_for_backward(xf, Wf, Uf, bf)
+        ctx.save_for_backward(xf, Wf, Uf, bf, *keep)
         return y.to(dt)
 
     @staticmethod
     def backward(ctx, dy):
         cell, rs, act, ract, hook, rev = ctx.cfg
-        saved = ctx.saved_tensors
+        saved = list(ctx.saved_tensors)
         xf, Wf, Uf, bf = saved[:4]
+        mask = saved.pop(4) if ctx.masked else None
         gW, gU, gb = ctx.grads
         if ctx.native:
             # fast path: dW/dU/db are accumulated into the fp32 arena slices in-kernel (None here)
             fp32 = lambda t: t if t is not None and t.dtype == torch.float32 and t.is_contiguous() else None
-            dx, dW, dU, db = C().rnn_bwd(cell, dy.float().contiguous(), xf, Wf, Uf, bf, rs, list(saved[4:]),
-                                         fp32(gW), fp32(gU), fp32(gb), ctx.needs_dx, *ctx.codes, rev)
+            extra = () if mask is None else (False, mask)
+            dx, dW, dU, db = C().rnn_bwd(cell, dy.float().contiguous(), xf, Wf, Uf, bf, rs, saved[4:],
+                                         fp32(gW), fp32(gU), fp32(gb), ctx.needs_dx, *ctx.codes, rev, *extra)
         else:
-            fn = lambda xx, ww, uu, bb: recurrent_ref(cell, xx, ww, uu, bb, rs, act, ract, rev)
+            fn = lambda xx, ww, uu, bb: recurrent_ref(cell, xx, ww, uu, bb, rs, act, ract, rev, mask)
             dx, dW, dU, db = ref_grads(fn, [xf, Wf, Uf, bf], dy.float())
         accumulate(gW, dW)
         accumulate(gU, dU)
         accumulate(gb, db)
         if hook is not None:
             hook()
-        return (None if dx is None else dx.to(dy.dtype)), None, None, None, None, None, None, None
+        return (None if dx is None else dx.to(dy.dtype)), None, None, None, None, None, None, None, None
+
+
+def _check_mask(mask, x):
+    if mask.dtype != torch.uint8 or mask.shape != x.shape[:2] or mask.device != x.device:
+        raise ValueError(f"mask must be uint8 [B, T] = {tuple(x.shape[:2])} on the input's device, got "
+                         f"{mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    return mask.contiguous()
 
 
 def recurrent(cell, x, W, U, b=None, *, grads=(None, None, None), return_sequences=False, activation="tanh",
-              recurrent_activation="hard_sigmoid", on_grad=None, go_backwards=False):
+              recurrent_activation="hard_sigmoid", on_grad=None, go_backwards=False, mask=None):
     gW, gU, gb = grads
     cfg = (cell, bool(return_sequences), activation, recurrent_activation, on_grad, bool(go_backwards))
-    return _RecurrentFn.apply(x, W, U, b, gW, gU, gb, cfg)
+    return _RecurrentFn.apply(x, W, U, b, gW, gU, gb, cfg, None if mask is None else _check_mask(mask, x))
 
 
 MERGE_MODES = ("concat", "sum", "ave")
@@ -150,26 +178,28 @@ class _BidirectionalFn(torch.autograd.Function):
     """(x, Wf, Uf, bf, Wb, Ub, bb) -> merged output of the forward and the backward direction."""
 
     @staticmethod
-    def forward(ctx, x, Wf, Uf, bf, Wb, Ub, bb, grads, cfg):
+    def forward(ctx, x, Wf, Uf, bf, Wb, Ub, bb, grads, cfg, mask=None):
         cell, rs, act, ract, hook, merge = cfg
         ctx.cfg, ctx.grads = cfg, grads
+        ctx.masked = mask is not None
+        keep = () if mask is None else (mask,)  # saved for the backward, not recomputed
         dt = x.dtype
         xf = x.float()
         ws = [None if t is None else t.float() for t in (Wf, Uf, bf, Wb, Ub, bb)]
         if use_native(x):
             ctx.codes = _act_codes(act, ract)
             y, saved = C().birnn_fwd(cell, xf.contiguous(), [ws[0], ws[3]], [ws[1], ws[4]], [ws[2], ws[5]], rs, merge,
-                                     *ctx.codes)
+                                     *ctx.codes, *keep)
             ctx.native = True
             ctx.needs_dx = ctx.needs_input_grad[0]
             ctx.has_b = (bf is not None, bb is not None)
-            ctx.save_for_backward(xf, *(t for t in ws if t is not None), *saved)
+            ctx.save_for_backward(xf, *keep, *(t for t in ws if t is not None), *saved)
             return y.to(dt)
         ctx.native = False
         with torch.no_grad():
-            y = bidirectional_ref(cell, xf, ws[:3], ws[3:], rs, merge, act, ract)
+            y = bidirectional_ref(cell, xf, ws[:3], ws[3:], rs, merge, act, ract, mask)
         ctx.has_b = (bf is not None, bb is not None)
-        ctx.save_for_backward(xf, *(t for t in ws if t is not None))
+        ctx.save_for_backward(xf, *keep, *(t for t in ws if t is not None))
         return y.to(dt)
 
     @staticmethod
@@ -177,6 +207,7 @@ class _BidirectionalFn(torch.autograd.Function):
         cell, rs, act, ract, hook, merge = ctx.cfg
         saved = list(ctx.saved_tensors)
         xf = saved.pop(0)
+        mask = saved.pop(0) if ctx.masked else None
         ws = []
         for has_b in ctx.has_b:
             ws += [saved.pop(0), saved.pop(0), saved.pop(0) if has_b else None]
@@ -186,7 +217,7 @@ class _BidirectionalFn(torch.autograd.Function):
             gg = [fp32(t) for t in g]
             dx, pg = C().birnn_bwd(cell, dy.float().contiguous(), xf, [ws[0], ws[3]], [ws[1], ws[4]], [ws[2], ws[5]],
                                    rs, merge, saved, [gg[0], gg[3]], [gg[1], gg[4]], [gg[2], gg[5]], ctx.needs_dx,
-                                   *ctx.codes)
+                                   *ctx.codes, *(() if mask is None else (mask,)))
             d = list(pg[0]) + list(pg[1])
         else:
             live = [t for t in ws if t is not None]
@@ -194,7 +225,7 @@ class _BidirectionalFn(torch.autograd.Function):
             def fn(xx, *flat):
                 it = iter(flat)
                 full = [None if t is None else next(it) for t in ws]
-                return bidirectional_ref(cell, xx, full[:3], full[3:], rs, merge, act, ract)
+                return bidirectional_ref(cell, xx, full[:3], full[3:], rs, merge, act, ract, mask)
 
             out = ref_grads(fn, [xf, *live], dy.float())
             dx, it = out[0], iter(out[1:])
@@ -203,16 +234,19 @@ class _BidirectionalFn(torch.autograd.Function):
             accumulate(buf, val)
         if hook is not None:
             hook()  # once: both directions' gradients are final here
-        return (None if dx is None else dx.to(dy.dtype)), None, None, None, None, None, None, None, None
+        return (None if dx is None else dx.to(dy.dtype)), None, None, None, None, None, None, None, None, None
 
 
 def bidirectional(cell, x, fwd, bwd, *, grads=((None, None, None), (None, None, None)), merge_mode="concat",
-                  return_sequences=False, activation="tanh", recurrent_activation="hard_sigmoid", on_grad=None):
+                  return_sequences=False, activation="tanh", recurrent_activation="hard_sigmoid", on_grad=None,
+                  mask=None):
     """Bidirectional recurrent layer as one autograd node.  ``fwd`` / ``bwd`` = (W, U, b | None) of the forward and the
     backward direction, ``grads`` their (gW, gU, gb) gradient buffers; the backward direction's sequence is
-    returned in input time order, merged by ``merge_mode`` (``concat`` / ``sum`` / ``ave``)."""
+    returned in input time order, merged by ``merge_mode`` (``concat`` / ``sum`` / ``ave``).  Both directions
+    read the same ``mask``."""
     if merge_mode not in MERGE_MODES:
         raise ValueError(f"merge_mode {merge_mode!r} is not supported (supported: {MERGE_MODES})")
     (Wf, Uf, bf), (Wb, Ub, bb) = (tuple(fwd) + (None,))[:3], (tuple(bwd) + (None,))[:3]
     cfg = (cell, bool(return_sequences), activation, recurrent_activation, on_grad, merge_mode)
-    return _BidirectionalFn.apply(x, Wf, Uf, bf, Wb, Ub, bb, tuple(tuple(t) for t in grads), cfg)
+    return _BidirectionalFn.apply(x, Wf, Uf, bf, Wb, Ub, bb, tuple(tuple(t) for t in grads), cfg,
+                                  None if mask is None else _check_mask(mask, x))

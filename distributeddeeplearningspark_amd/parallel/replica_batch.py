@@ -71,6 +71,8 @@ def why_not(group) -> str | None:
         m = r.model
         ls = _layers(m)
         if ls is None:
+            if m._masked:
+                return "masked recurrent model (the batched kernels take no step mask)"
             return "not a GRU/LSTM -> Dense Sequential"
         if m.loss != "mean_squared_error" or m.arena.compute is not m.arena.master:
             return "loss is not MSE or compute is not fp32"

@@ -342,7 +342,8 @@ class ReplicaGroup:
                 return True
             except ValueError as e:  # a launch-plan shape the batched kernels do not cover: per-replica path
                 why_seq = str(e)
-        is_rnn = replica_batch._layers(self.reps[0].model) is not None
+        m0 = self.reps[0].model
+        is_rnn = replica_batch._layers(m0) is not None or m0._masked
         self.batch_reason = why_rnn if is_rnn else why_seq
         if self.batch_reason != "DDL_REPLICA_BATCH=0":
             print(f"[ddl] replica group of {len(self.reps)} runs per replica (not batched): {self.batch_reason}",

@@ -98,5 +98,42 @@ def history_executors_average(history):
     return [float(np.mean([h[i] for h in history])) for i in range(n)]
 
 
-__all__ = ["get_os_username", "serialize_keras_model", "deserialize_keras_model", "uniform_weights",
+def pad_sequences(sequences, maxlen=None, dtype="int32", padding="pre", truncating="pre", value=0.0):
+    """Keras ``pad_sequences``: a list of sequences (of scalars or of equal-shaped steps) -> one array
+    ``[len(sequences), maxlen, ...]``.  Shorter sequences are filled with ``value`` before (``padding="pre"``,
+    the default) or after (``"post"``) their steps; longer ones lose steps from the front (``truncating="pre"``)
+    or the back.  ``maxlen=None`` takes the longest sequence.  With ``value`` 0 the padded id column is what
+    ``Embedding(mask_zero=True)`` masks."""
+    if padding not in ("pre", "post"):
+        raise ValueError(f'Padding type "{padding}" not understood')
+    if truncating not in ("pre", "post"):
+        raise ValueError(f'Truncating type "{truncating}" not understood')
+    try:
+        lengths = [len(s) for s in sequences]
+    except TypeError:
+        raise ValueError("`sequences` must be a list of iterables") from None
+    if maxlen is None:
+        maxlen = max(lengths, default=0)
+    maxlen = int(maxlen)
+    step_shape = ()
+    for s in sequences:  # shape of one step, from the first non-empty sequence
+        if len(s):
+            step_shape = np.asarray(s).shape[1:]
+            break
+    out = np.full((len(lengths), maxlen) + tuple(step_shape), value, dtype=dtype)
+    for i, s in enumerate(sequences):
+        if not len(s) or not maxlen:
+            continue
+        trunc = np.asarray(s[-maxlen:] if truncating == "pre" else s[:maxlen], dtype=dtype)
+        if trunc.shape[1:] != tuple(step_shape):
+            raise ValueError(f"Shape of sample {trunc.shape[1:]} of sequence at position {i} is different from "
+                             f"expected shape {tuple(step_shape)}")
+        if padding == "post":
+            out[i, : len(trunc)] = trunc
+        else:
+            out[i, maxlen - len(trunc):] = trunc
+    return out
+
+
+__all__ = ["get_os_username", "pad_sequences", "serialize_keras_model", "deserialize_keras_model", "uniform_weights",
            "weights_mean", "shuffle", "precache", "history_executors_average", "set_states", "get_states"]
