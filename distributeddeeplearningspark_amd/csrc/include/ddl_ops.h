@@ -312,7 +312,22 @@ struct RnnDir {
   int ldy;
   float dscale;
   const unsigned char* mask;  // [B][T] in memory time order, shared by the directions; null: every step is data
+  const float* rdp[2];  // [G][B][H] recurrent dropout multipliers of the direction (DROP instantiations), or null
 };
+// Dropout masks (Keras dropout / recurrent_dropout, implementation = 1): fp32 multipliers dp [G][B][I] on the input and
+// rdp [G][B][H] on the recurrent state, one per gate, constant over the T steps.  Gate g contracts h * rdp[g] (the GRU
+// candidate r * h * rdp[2]) against U_g; the element-wise state updates keep the unmasked h.  A launch with rdp set
+// in every direction runs the DROP instantiations: xw must be given (the projection is never fused), and the
+// register-resident kernels run one batch row per workgroup with the row's mask folded into the U registers.
+// The input masks never reach the recurrence: rnn_drop_x writes the G masked copies xm [G][B T][I] = x * dp[g] for
+// the per-gate projection GEMMs, rnn_drop_dx reduces their gradients, dx (+)= sum_g t[g] * dp[g] with t [G][B T][I].
+int rnn_drop_x(const float* x, const float* dp, float* xm, int G, int B, int T, int I, hipStream_t s);
+int rnn_drop_dx(const float* t, const float* dp, float* dx, int G, int B, int T, int I, int accumulate, hipStream_t s);
+// rnn_param_grad with either mask (nullable): gU_g += (h_{t-1} * rdp[g])^T dg_g (GRU candidate: r * h_{t-1} * rdp[2]),
+// gW_g += (x * dp[g])^T dg_g; tiled per gate, so every cell and width is served
+int rnn_param_grad_drop(int cell, const float* dg, const float* hs, const float* gates, const float* x, const float* dp,
+                        const float* rdp, float* gU, float* gW, float* gb, int B, int T, int H, int I, hipStream_t s,
+                        int rev);
 int rnn_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
                 int ract, hipStream_t s);
 int rnn_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract, hipStream_t s);

@@ -23,6 +23,15 @@
 // c) over in the element-wise state update and writes the carried state to the "next" slots and to y; backward it
 // emits zero gate gradients and hands dh (dc) on unchanged.  Contractions and barriers are those of MASK = false,
 // and with MASK = false no mask code is generated.
+//
+// Dropout instantiations (DROP = true, directed only, never with REP or the fused input projection; Keras
+// recurrent_dropout, implementation = 1): RnnDir::rdp[d] holds the direction's fp32 multipliers [G][B][H], constant over
+// the steps.  Gate g contracts h * rdp[g] (the GRU candidate r * h * rdp[2]); the element-wise updates keep the unmasked
+// h.  The generic kernels stage the workgroup's rows of the masks in LDS once (forward) or apply them per gate to the
+// U^T contractions (backward).  The register-resident kernels run one batch row per workgroup and fold the row's mask
+// into the U registers as they are loaded, (h * m) U = h (diag(m) U): step loop, barriers and prefetch are untouched.
+// Input dropout never reaches these kernels (masked projection up front: rnn_drop_x / rnn_drop_dx below); the
+// parameter-gradient kernel has a DROP variant tiled per gate.  With DROP = false no dropout code is generated.
 #include <type_traits>
 
 #include "ddl_act.h"
@@ -85,12 +94,13 @@ __device__ __forceinline__ float hsig(float x) { return fminf(fmaxf(0.2f * x + 0
 __device__ __forceinline__ float hsig_d(float y) { return (y > 0.f && y < 1.f) ? 0.2f : 0.f; }
 
 // ----------------------------------------------------------------------------- forward
-template <int CELL, bool DIR = false, bool MASK = false>  // 0 = GRU (gates z, r, h), 1 = LSTM (gates i, f, c, o), 2 = SimpleRNN (h)
+template <int CELL, bool DIR = false, bool MASK = false, bool DROP = false>  // 0 = GRU (gates z, r, h), 1 = LSTM (gates i, f, c, o), 2 = SimpleRNN (h)
 __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ xw, const float* __restrict__ U,
                                                       float* __restrict__ hs, float* __restrict__ cs,
                                                       float* __restrict__ gates, float* __restrict__ y, int B, int T,
                                                       int H, int rs, int act, int ract, const DirArg<DIR> dr) {
   static_assert(DIR || !MASK, "masked recurrences run as directed launches");
+  static_assert(DIR || !DROP, "recurrences with dropout masks run as directed launches");
   constexpr int G = CELL == 0 ? 3 : (CELL == 1 ? 4 : 1);
   extern __shared__ float sm[];
   const int GH = G * H;
@@ -103,8 +113,16 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
   float* h = sm;              // [BB][H]
   float* c = h + BB * H;      // [BB][H]   (LSTM) / r*h (GRU)
   float* gb = c + BB * H;     // [BB][GH]  gate values of the current step
+  float* rd = gb + BB * GH;   // [G][BB][H] recurrent dropout multipliers of the workgroup's rows (DROP only)
   const int b0 = blockIdx.x * BB;
   const int nb = min(BB, B - b0);
+  if constexpr (DROP) {
+    const float* rdp = dr.rdp[blockIdx.y];
+    for (int i = threadIdx.x; i < G * BB * H; i += blockDim.x) {
+      const int g = i / (BB * H), q = i - g * BB * H, r = q / H, k = q - r * H;
+      rd[i] = r < nb ? rdp[((long)g * B + b0 + r) * H + k] : 0.f;
+    }
+  }
   for (int i = threadIdx.x; i < BB * H; i += blockDim.x) h[i] = c[i] = 0.f;
   for (int i = threadIdx.x; i < nb * H; i += blockDim.x) {
     const int r = i / H, k = i - r * H;
@@ -120,10 +138,19 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
       float acc[BB];
 #pragma unroll
       for (int r = 0; r < BB; ++r) acc[r] = r < nb ? xw[((long)(b0 + r) * T + t) * GH + j] : 0.f;
-      for (int k = 0; k < H; ++k) {
-        const float u = U[(long)k * GH + j];
+      if constexpr (DROP) {
+        const float* rg = rd + (j / H) * BB * H;  // the masks of column j's gate
+        for (int k = 0; k < H; ++k) {
+          const float u = U[(long)k * GH + j];
 #pragma unroll
-        for (int r = 0; r < BB; ++r) acc[r] += h[r * H + k] * u;
+          for (int r = 0; r < BB; ++r) acc[r] += h[r * H + k] * rg[r * H + k] * u;
+        }
+      } else {
+        for (int k = 0; k < H; ++k) {
+          const float u = U[(long)k * GH + j];
+#pragma unroll
+          for (int r = 0; r < BB; ++r) acc[r] += h[r * H + k] * u;
+        }
       }
       // LSTM candidate and SimpleRNN use the activation, every other gate the recurrent one
       const bool main_act = CELL == 2 || (CELL == 1 && j >= 2 * H && j < 3 * H);
@@ -135,6 +162,7 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
       for (int i = threadIdx.x; i < BB * H; i += blockDim.x) {
         const int r = i / H, k = i - r * H;
         c[i] = gb[r * GH + H + k] * h[i];  // r * h
+        if constexpr (DROP) c[i] *= rd[2 * BB * H + i];  // read only by the candidate's contraction
       }
       __syncthreads();
       for (int j = 2 * H + threadIdx.x; j < GH; j += blockDim.x) {
@@ -185,17 +213,20 @@ __global__ __launch_bounds__(512) void rnn_fwd_kernel(const float* __restrict__ 
 
 // ----------------------------------------------------------------------------- backward
 // UT = U^T [GH][H]; dgates [B][T][GH] = d(pre-activation)
-template <int CELL, bool DIR = false, bool MASK = false>
+template <int CELL, bool DIR = false, bool MASK = false, bool DROP = false>
 __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ UT,
                                                       const float* __restrict__ hs, const float* __restrict__ cs,
                                                       const float* __restrict__ gates, float* __restrict__ dgates,
                                                       int B, int T, int H, int rs, int act, int ract,
                                                       const DirArg<DIR> dr) {
   static_assert(DIR || !MASK, "masked recurrences run as directed launches");
+  static_assert(DIR || !DROP, "recurrences with dropout masks run as directed launches");
   constexpr int G = CELL == 0 ? 3 : (CELL == 1 ? 4 : 1);
   extern __shared__ float sm[];
   const int GH = G * H;
   DirOf<DIR> dz;
+  const float* rdp = nullptr;  // [G][B][H] (DROP only)
+  if constexpr (DROP) rdp = dr.rdp[blockIdx.y];
   if constexpr (DIR) {
     const int d = blockIdx.y;
     dy = dr.dy[d]; UT = dr.UT[d]; hs = dr.hs[d]; cs = dr.cs[d]; gates = dr.gates[d]; dgates = dr.dgates[d];
@@ -255,6 +286,7 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
         const float* p = dp + r * GH;
         float drh = 0.f;
         for (int j = 0; j < H; ++j) drh += p[2 * H + j] * UT[(long)(2 * H + j) * H + k];
+        if constexpr (DROP) drh *= rdp[((long)2 * B + row) * H + k];  // d(r*h) through (r * h * rdp[2]) Uh
         const float hp = hs[dz.prev_slot(row, T, t) * H + k];
         const float rg = gates[(row * T + t) * GH + H + k];
         if constexpr (MASK) {
@@ -274,7 +306,15 @@ __global__ __launch_bounds__(512) void rnn_bwd_kernel(const float* __restrict__ 
       if constexpr (MASK) {
         if (!dr.mask[(long)(b0 + r) * T + t]) s = dh[i];  // the carried dh; every p[j] of the row is zero
       }
-      for (int j = 0; j < jend; ++j) s += p[j] * UT[(long)j * H + k];
+      if constexpr (DROP) {  // gate g's contraction read h * rdp[g]
+        for (int g = 0; g * H < jend; ++g) {
+          float sg = 0.f;
+          for (int j = g * H; j < (g + 1) * H; ++j) sg += p[j] * UT[(long)j * H + k];
+          s += sg * rdp[((long)g * B + b0 + r) * H + k];
+        }
+      } else {
+        for (int j = 0; j < jend; ++j) s += p[j] * UT[(long)j * H + k];
+      }
       dh[i] = s;
     }
     for (int i = threadIdx.x; i < nb * GH; i += blockDim.x) {
@@ -341,7 +381,9 @@ constexpr int bwd_threads() { return H * (((CELL == 0 ? 3 : 4) * H / 64) <= 4 ? 
 // DIR: directed (RnnDir): blockIdx.y is the direction; xw / W / bias / U / hs / cs / gates / y come from its table entry.
 // MASK: masked steps (RnnDir::mask) carry the state over; the byte of the element this thread owns in the state
 // update is prefetched with the step's inputs.
-template <int CELL, int H, int BB_, bool FUSE, bool REP = false, bool DIR = false, bool MASK = false>
+// DROP: recurrent dropout (RnnDir::rdp) at one batch row per workgroup: the row's multipliers of column j's gate scale
+// the thread's U slice once, in the prologue.
+template <int CELL, int H, int BB_, bool FUSE, bool REP = false, bool DIR = false, bool MASK = false, bool DROP = false>
 __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     const float* __restrict__ xw, const float* __restrict__ x, const float* __restrict__ W,
     const float* __restrict__ bias, int I, const float* __restrict__ U, float* __restrict__ hs,
@@ -349,6 +391,7 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     const RegArg<DIR> rp) {
   static_assert(!(REP && DIR), "replica batching is forward-only");
   static_assert(DIR || !MASK, "masked recurrences run as directed launches");
+  static_assert(!DROP || (DIR && !FUSE && BB_ == 1), "dropout: directed, projection precomputed, one row per workgroup");
   constexpr int G = CELL == 0 ? 3 : 4;
   constexpr int GH = G * H;
   constexpr int KS = H / CH;
@@ -378,8 +421,29 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
     dz.load(rp, d);
   }
   float u[CH];
+  if constexpr (DROP) {  // (h * m) U = h (diag(m) U): b0 is the workgroup's only row, j / H its gate
+    // Sixteen U elements and their multipliers per round trip: the 64 strided U loads at once already fill the
+    // register budget with their addresses (LSTM(128): 1024 threads, 128 VGPRs) and would spill beside the mask's.
+    const float* m = rp.rdp[blockIdx.y] + ((long)(j / H) * B + b0) * H + kh * CH;
 #pragma unroll
-  for (int i = 0; i < CH; ++i) u[i] = U[(long)(kh * CH + i) * GH + j];
+    for (int i0 = 0; i0 < CH; i0 += 16) {
+      float mv[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        u[i0 + i] = U[(long)(kh * CH + i0 + i) * GH + j];
+        mv[i] = m[i0 + i];
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        u[i0 + i] *= mv[i];
+        asm volatile("" : "+v"(u[i0 + i]));  // the product exists here: U element and multiplier are not both kept
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < CH; ++i) u[i] = U[(long)(kh * CH + i) * GH + j];
+  }
   float wv[IMAX], bv = 0.f;  // input-projection column j (fused path); wv[i] = 0 past the input width
 #pragma unroll
   for (int i = 0; i < IMAX; ++i) wv[i] = (FUSE && i < I) ? W[(long)i * GH + j] : 0.f;
@@ -524,13 +588,16 @@ __global__ __launch_bounds__((fwd_threads<CELL, H>())) void rnn_fwd_reg_kernel(
 
 // MASK: a masked step (RnnDir::mask, its byte prefetched with the step's saved activations) writes zero gate
 // gradients and hands dh on through the direct-part row (GRU: aux, LSTM: the otherwise unused hpl); dc stays in aux.
-template <int CELL, int H, int BB_, bool REP = false, bool DIR = false, bool MASK = false>
+// DROP: as forward, the row's multipliers fold into the U registers: thread (k, js) scales its chunk, which lies inside
+// one gate (H is a multiple of 64), by rdp[gate][row][k].
+template <int CELL, int H, int BB_, bool REP = false, bool DIR = false, bool MASK = false, bool DROP = false>
 __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
     const float* __restrict__ dy, const float* __restrict__ U, const float* __restrict__ hs,
     const float* __restrict__ cs, const float* __restrict__ gates, float* __restrict__ dgates, int B, int T, int rs,
     const RegArg<DIR> rp) {
   static_assert(!(REP && DIR), "replica batching is forward-only");
   static_assert(DIR || !MASK, "masked recurrences run as directed launches");
+  static_assert(!DROP || (DIR && BB_ == 1 && H % CH == 0), "dropout: directed, one row per workgroup");
   constexpr int G = CELL == 0 ? 3 : 4;
   constexpr int GH = G * H;
   constexpr int JS = GH / CH;                            // column chunks
@@ -559,6 +626,12 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
   for (int i = 0; i < CH; i += 4) {
     const float4 v = *reinterpret_cast<const float4*>(&U[(long)k * GH + min(js, JS - 1) * CH + i]);  // idle: unused
     u[i] = v.x; u[i + 1] = v.y; u[i + 2] = v.z; u[i + 3] = v.w;
+  }
+  if constexpr (DROP) {
+    const int g = min(js, JS - 1) * CH / H;  // the gate of this thread's column chunk
+    const float m = rp.rdp[blockIdx.y][((long)g * B + b0) * H + k];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) u[i] *= m;
   }
   for (int i = tid; i < BB_ * H; i += NT) (&dh[0][0])[i] = (&aux[0][0])[i] = 0.f;
   if constexpr (MASK && CELL == 1) {  // rows past the batch are never written
@@ -679,23 +752,39 @@ __global__ __launch_bounds__((bwd_threads<CELL, H>())) void rnn_bwd_reg_kernel(
 // chunk of PG_BT (b,t) rows staged in LDS; 256 threads x 4x4 outputs.
 constexpr int PG_BT = 128;
 
+struct DropMasks {
+  const float* dp;   // [G][B][I] input multipliers or null
+  const float* rdp;  // [G][B][H] recurrent multipliers or null
+};
+template <bool DROP>
+using DropArg = std::conditional_t<DROP, DropMasks, NoDir>;
+
 // REV: saved tensors of a reverse-direction recurrence, h_{t-1} in slot t + 1
-template <int CELL, bool REV = false>
+// DROP: the A rows carry gate g's dropout multipliers (h_{t-1} * rdp[g], x * dp[g]), so a j tile stays inside one
+// gate: blockIdx.y = gate * ceil(H / 64) + tile of the gate's H columns (any H, GRU included).
+template <int CELL, bool REV = false, bool DROP = false>
 __global__ __launch_bounds__(256) void rnn_param_grad_kernel(const float* __restrict__ dg, const float* __restrict__ hs,
                                                              const float* __restrict__ gates,
                                                              const float* __restrict__ x, float* __restrict__ gU,
                                                              float* __restrict__ gW, float* __restrict__ gb, int B,
-                                                             int T, int H, int I) {
+                                                             int T, int H, int I, const DropArg<DROP> dm) {
   constexpr int G = CELL == 0 ? 3 : (CELL == 1 ? 4 : 1);
   const int GH = G * H;
   const int M = H + I + (gb ? 1 : 0);
   const long BT = (long)B * T;
-  const int m0 = blockIdx.x * 64, j0 = blockIdx.y * 64;
+  const int m0 = blockIdx.x * 64;
+  int j0 = blockIdx.y * 64, jend = GH, gate = 0;  // columns [j0, min(j0 + 64, jend)) of dg
+  if constexpr (DROP) {
+    const int tiles = (H + 63) / 64;
+    gate = blockIdx.y / tiles;
+    j0 = gate * H + (blockIdx.y - gate * tiles) * 64;
+    jend = (gate + 1) * H;
+  }
   const long bt0 = (long)blockIdx.z * PG_BT;
   const int nbt = (int)min((long)PG_BT, BT - bt0);
   __shared__ float As[PG_BT][64 + 1];
   __shared__ float Ds[PG_BT][64 + 1];
-  const bool cand = CELL == 0 && j0 >= 2 * H;  // 2H is a multiple of 64
+  const bool cand = CELL == 0 && (DROP ? gate == 2 : j0 >= 2 * H);  // not DROP: 2H is a multiple of 64
   // fill: thread owns column c and rows q = q0, q0+4, ...; (b, t) advance incrementally
   // (a runtime-T division per element would dominate the kernel)
   const int c = threadIdx.x & 63, q0 = threadIdx.x >> 6;
@@ -708,14 +797,20 @@ __global__ __launch_bounds__(256) void rnn_param_grad_kernel(const float* __rest
     if (m < H) {
       a = hs[(b * (T + 1) + t + (REV ? 1 : 0)) * H + m];
       if (cand) a *= gates[bt * GH + H + m];
+      if constexpr (DROP) {
+        if (dm.rdp) a *= dm.rdp[((long)gate * B + b) * H + m];
+      }
     } else if (m < H + I) {
       a = x[bt * I + (m - H)];
+      if constexpr (DROP) {
+        if (dm.dp) a *= dm.dp[((long)gate * B + b) * I + (m - H)];
+      }
     } else if (m < M) {
       a = 1.f;
     }
     As[q][c] = a;
     const int jj = j0 + c;
-    Ds[q][c] = jj < GH ? dg[bt * GH + jj] : 0.f;
+    Ds[q][c] = jj < jend ? dg[bt * GH + jj] : 0.f;
   }
   __syncthreads();
   const int tm = (threadIdx.x / 16) * 4, tj = (threadIdx.x % 16) * 4;
@@ -737,7 +832,7 @@ __global__ __launch_bounds__(256) void rnn_param_grad_kernel(const float* __rest
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const int jj = j0 + tj + l;
-      if (jj < GH) atomicAdd(dst + jj, acc[i][l]);
+      if (jj < jend) atomicAdd(dst + jj, acc[i][l]);
     }
   }
 }
@@ -770,84 +865,105 @@ int launch_bwd_reg(const float* dy, const float* U, const float* hs, const float
   return (int)hipGetLastError();
 }
 
-// directed launches: grid.y = direction, everything per direction comes from the table (MASK: d.mask is set)
-template <int CELL, int H, int BB_, bool MASK>
+// directed launches: grid.y = direction, everything per direction comes from the table (MASK: d.mask is set;
+// DROP: d.rdp is set in every direction and the projection d.xw is given)
+template <int CELL, int H, int BB_, bool MASK, bool DROP>
 int launch_fwd_reg_dir(const RnnDir& d, int ndir, const float* x, int I, int B, int T, int rs, hipStream_t s) {
   const bool fuse = !d.xw[0];
-  if (fuse && (I < 1 || I > IMAX)) return (int)hipErrorInvalidValue;
+  if (fuse && (DROP || I < 1 || I > IMAX)) return (int)hipErrorInvalidValue;
   const dim3 grid((B + BB_ - 1) / BB_, ndir), block(fwd_threads<CELL, H>());
   const float* const np = nullptr;
   float* const nq = nullptr;
-  if (fuse)
-    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, true, false, true, MASK>), grid, block, 0, s, np, x, np, np,
-                       I, np, nq, nq, nq, nq, B, T, rs, d);
-  else
-    hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, false, false, true, MASK>), grid, block, 0, s, np, x, np, np,
-                       I, np, nq, nq, nq, nq, B, T, rs, d);
+  if constexpr (!DROP) {
+    if (fuse) {
+      hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, true, false, true, MASK>), grid, block, 0, s, np, x, np, np,
+                         I, np, nq, nq, nq, nq, B, T, rs, d);
+      return (int)hipGetLastError();
+    }
+  }
+  hipLaunchKernelGGL((rnn_fwd_reg_kernel<CELL, H, BB_, false, false, true, MASK, DROP>), grid, block, 0, s, np, x, np,
+                     np, I, np, nq, nq, nq, nq, B, T, rs, d);
   return (int)hipGetLastError();
 }
 
-template <int CELL, int H, int BB_, bool MASK>
+template <int CELL, int H, int BB_, bool MASK, bool DROP>
 int launch_bwd_reg_dir(const RnnDir& d, int ndir, int B, int T, int rs, hipStream_t s) {
   const dim3 grid((B + BB_ - 1) / BB_, ndir);
   const float* const np = nullptr;
-  hipLaunchKernelGGL((rnn_bwd_reg_kernel<CELL, H, BB_, false, true, MASK>), grid, dim3(bwd_threads<CELL, H>()), 0, s,
-                     np, np, np, np, np, (float*)nullptr, B, T, rs, d);
+  hipLaunchKernelGGL((rnn_bwd_reg_kernel<CELL, H, BB_, false, true, MASK, DROP>), grid, dim3(bwd_threads<CELL, H>()), 0,
+                     s, np, np, np, np, np, (float*)nullptr, B, T, rs, d);
   return (int)hipGetLastError();
 }
 
-template <bool MASK>
+// dynamic LDS of the generic kernels: h, c / aux and the gate rows of BB batch rows; forward DROP: plus the staged masks.
+// Past the 64 KB a launch gets by default the kernel is granted the larger size; 160 KB is the CU's LDS.
+constexpr size_t kLdsDefault = 64 * 1024, kLdsMax = 160 * 1024;
+template <typename K>
+int grant_lds(K kernel, size_t lds) {
+  if (lds <= kLdsDefault) return 0;
+  if (lds > kLdsMax) return (int)hipErrorInvalidValue;
+  return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+}
+
+template <int CELL, bool MASK, bool DROP>
+int launch_fwd_gen_dir(const RnnDir& d, const dim3 grid, int threads, size_t lds, int B, int T, int H, int rs, int act,
+                       int ract, hipStream_t s) {
+  const float* const np = nullptr;
+  float* const nq = nullptr;
+  if constexpr (DROP) {
+    if (const int e = grant_lds(rnn_fwd_kernel<CELL, true, MASK, DROP>, lds)) return e;
+  }
+  hipLaunchKernelGGL((rnn_fwd_kernel<CELL, true, MASK, DROP>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T,
+                     H, rs, act, ract, d);
+  return (int)hipGetLastError();
+}
+
+template <bool MASK, bool DROP>
 int launch_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
                    int ract, hipStream_t s) {
   const bool reg = rnn_reg_path(cell, H, act, ract);
+  constexpr int BB128 = DROP ? 1 : RNN_BB_FWD, BB64 = DROP ? 1 : 2;  // DROP: one row per workgroup (mask folded into U)
   if (reg && H == 128)
-    return cell == 0 ? launch_fwd_reg_dir<0, 128, RNN_BB_FWD, MASK>(d, ndir, x, I, B, T, rs, s)
-                     : launch_fwd_reg_dir<1, 128, RNN_BB_FWD, MASK>(d, ndir, x, I, B, T, rs, s);
+    return cell == 0 ? launch_fwd_reg_dir<0, 128, BB128, MASK, DROP>(d, ndir, x, I, B, T, rs, s)
+                     : launch_fwd_reg_dir<1, 128, BB128, MASK, DROP>(d, ndir, x, I, B, T, rs, s);
   if (reg && H == 64)
-    return cell == 0 ? launch_fwd_reg_dir<0, 64, 2, MASK>(d, ndir, x, I, B, T, rs, s)
-                     : launch_fwd_reg_dir<1, 64, 2, MASK>(d, ndir, x, I, B, T, rs, s);
+    return cell == 0 ? launch_fwd_reg_dir<0, 64, BB64, MASK, DROP>(d, ndir, x, I, B, T, rs, s)
+                     : launch_fwd_reg_dir<1, 64, BB64, MASK, DROP>(d, ndir, x, I, B, T, rs, s);
   if (!d.xw[0]) return (int)hipErrorInvalidValue;  // generic kernels need the projection precomputed
   const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
-  const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
+  const size_t lds = sizeof(float) * (2 * BB * H + (DROP ? 2 : 1) * BB * G * H);
   const int threads = std::min(512, ((G * H + 63) / 64) * 64);
   const dim3 grid((B + BB - 1) / BB, ndir);
-  const float* const np = nullptr;
-  float* const nq = nullptr;
-  if (cell == 0)
-    hipLaunchKernelGGL((rnn_fwd_kernel<0, true, MASK>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H,
-                       rs, act, ract, d);
-  else if (cell == 1)
-    hipLaunchKernelGGL((rnn_fwd_kernel<1, true, MASK>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H,
-                       rs, act, ract, d);
-  else
-    hipLaunchKernelGGL((rnn_fwd_kernel<2, true, MASK>), grid, dim3(threads), lds, s, np, np, nq, nq, nq, nq, B, T, H,
-                       rs, act, ract, d);
-  return (int)hipGetLastError();
+  if (cell == 0) return launch_fwd_gen_dir<0, MASK, DROP>(d, grid, threads, lds, B, T, H, rs, act, ract, s);
+  if (cell == 1) return launch_fwd_gen_dir<1, MASK, DROP>(d, grid, threads, lds, B, T, H, rs, act, ract, s);
+  return launch_fwd_gen_dir<2, MASK, DROP>(d, grid, threads, lds, B, T, H, rs, act, ract, s);
 }
 
-template <bool MASK>
+template <bool MASK, bool DROP>
 int launch_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract,
                    hipStream_t s) {
   const bool reg = rnn_reg_path(cell, H, act, ract);
+  constexpr int BB128 = DROP ? 1 : RNN_BB_BWD, BB64 = DROP ? 1 : 2;
   if (reg && H == 128)
-    return cell == 0 ? launch_bwd_reg_dir<0, 128, RNN_BB_BWD, MASK>(d, ndir, B, T, rs, s)
-                     : launch_bwd_reg_dir<1, 128, RNN_BB_BWD, MASK>(d, ndir, B, T, rs, s);
+    return cell == 0 ? launch_bwd_reg_dir<0, 128, BB128, MASK, DROP>(d, ndir, B, T, rs, s)
+                     : launch_bwd_reg_dir<1, 128, BB128, MASK, DROP>(d, ndir, B, T, rs, s);
   if (reg && H == 64)
-    return cell == 0 ? launch_bwd_reg_dir<0, 64, 2, MASK>(d, ndir, B, T, rs, s)
-                     : launch_bwd_reg_dir<1, 64, 2, MASK>(d, ndir, B, T, rs, s);
+    return cell == 0 ? launch_bwd_reg_dir<0, 64, BB64, MASK, DROP>(d, ndir, B, T, rs, s)
+                     : launch_bwd_reg_dir<1, 64, BB64, MASK, DROP>(d, ndir, B, T, rs, s);
   const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
   const size_t lds = sizeof(float) * (2 * BB * H + BB * G * H);
   const int threads = std::min(512, ((G * H + 63) / 64) * 64);
   const dim3 grid((B + BB - 1) / BB, ndir);
   const float* const np = nullptr;
   if (cell == 0)
-    hipLaunchKernelGGL((rnn_bwd_kernel<0, true, MASK>), grid, dim3(threads), lds, s, np, np, np, np, np,
+    hipLaunchKernelGGL((rnn_bwd_kernel<0, true, MASK, DROP>), grid, dim3(threads), lds, s, np, np, np, np, np,
                        (float*)nullptr, B, T, H, rs, act, ract, d);
   else if (cell == 1)
-    hipLaunchKernelGGL((rnn_bwd_kernel<1, true, MASK>), grid, dim3(threads), lds, s, np, np, np, np, np,
+    hipLaunchKernelGGL((rnn_bwd_kernel<1, true, MASK, DROP>), grid, dim3(threads), lds, s, np, np, np, np, np,
                        (float*)nullptr, B, T, H, rs, act, ract, d);
   else
-    hipLaunchKernelGGL((rnn_bwd_kernel<2, true, MASK>), grid, dim3(threads), lds, s, np, np, np, np, np,
+    hipLaunchKernelGGL((rnn_bwd_kernel<2, true, MASK, DROP>), grid, dim3(threads), lds, s, np, np, np, np, np,
                        (float*)nullptr, B, T, H, rs, act, ract, d);
   return (int)hipGetLastError();
 }
@@ -881,6 +997,31 @@ __global__ __launch_bounds__(256) void mask_apply_kernel(const float* __restrict
   const long n = rows * F;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
     out[i] = mask[i / F] ? in[i] : 0.f;
+}
+
+// Input dropout (Keras dropout on a recurrent layer): xm [G][B T][I] = x [B T][I] * dp [G][B][I], the G masked
+// copies the per-gate projection GEMMs read
+__global__ __launch_bounds__(256) void rnn_drop_x_kernel(const float* __restrict__ x, const float* __restrict__ dp,
+                                                         float* __restrict__ xm, int G, int B, int T, int I) {
+  const long per = (long)B * T * I, n = G * per;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long g = i / per, q = i - g * per, b = q / ((long)T * I);
+    xm[i] = x[q] * dp[(g * B + b) * I + q % I];
+  }
+}
+
+// ... and its gradient: dx [B T][I] (+)= sum_g t [G][B T][I] * dp [G][B][I]
+__global__ __launch_bounds__(256) void rnn_drop_dx_kernel(const float* __restrict__ t, const float* __restrict__ dp,
+                                                          float* __restrict__ dx, int G, int B, int T, int I,
+                                                          int accumulate) {
+  const long per = (long)B * T * I;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < per; q += (long)gridDim.x * 256) {
+    const long b = q / ((long)T * I);
+    const int i = (int)(q % I);
+    float a = accumulate ? dx[q] : 0.f;
+    for (int g = 0; g < G; ++g) a += t[g * per + q] * dp[((long)g * B + b) * I + i];
+    dx[q] = a;
+  }
 }
 
 __global__ __launch_bounds__(256) void mask_from_ids_kernel(const long* __restrict__ ids,
@@ -930,21 +1071,68 @@ int rnn_param_grad(int cell, const float* dg, const float* hs, const float* gate
   const int M = H + I + (gb ? 1 : 0);
   const long BT = (long)B * T;
   const dim3 grid((M + 63) / 64, (G * H + 63) / 64, (unsigned)((BT + PG_BT - 1) / PG_BT));
+  const NoDir nd{};
   if (rev) {
     if (cell == 0)
-      hipLaunchKernelGGL((rnn_param_grad_kernel<0, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+      hipLaunchKernelGGL((rnn_param_grad_kernel<0, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, nd);
     else if (cell == 1)
-      hipLaunchKernelGGL((rnn_param_grad_kernel<1, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+      hipLaunchKernelGGL((rnn_param_grad_kernel<1, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, nd);
     else
-      hipLaunchKernelGGL((rnn_param_grad_kernel<2, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+      hipLaunchKernelGGL((rnn_param_grad_kernel<2, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, nd);
     return (int)hipGetLastError();
   }
   if (cell == 0)
-    hipLaunchKernelGGL(rnn_param_grad_kernel<0>, grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+    hipLaunchKernelGGL(rnn_param_grad_kernel<0>, grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, nd);
   else if (cell == 1)
-    hipLaunchKernelGGL(rnn_param_grad_kernel<1>, grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+    hipLaunchKernelGGL(rnn_param_grad_kernel<1>, grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, nd);
   else
-    hipLaunchKernelGGL(rnn_param_grad_kernel<2>, grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I);
+    hipLaunchKernelGGL(rnn_param_grad_kernel<2>, grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, nd);
+  return (int)hipGetLastError();
+}
+
+namespace {
+template <int CELL, bool REV>
+void launch_param_grad_drop(const dim3 grid, hipStream_t s, const float* dg, const float* hs, const float* gates,
+                            const float* x, float* gU, float* gW, float* gb, int B, int T, int H, int I,
+                            const DropMasks dm) {
+  hipLaunchKernelGGL((rnn_param_grad_kernel<CELL, REV, true>), grid, dim3(256), 0, s, dg, hs, gates, x, gU, gW, gb, B, T,
+                     H, I, dm);
+}
+}  // namespace
+
+int rnn_param_grad_drop(int cell, const float* dg, const float* hs, const float* gates, const float* x, const float* dp,
+                        const float* rdp, float* gU, float* gW, float* gb, int B, int T, int H, int I, hipStream_t s,
+                        int rev) {
+  const int G = cell == 0 ? 3 : (cell == 1 ? 4 : 1);
+  const int M = H + I + (gb ? 1 : 0);
+  const long BT = (long)B * T;
+  const dim3 grid((M + 63) / 64, G * ((H + 63) / 64), (unsigned)((BT + PG_BT - 1) / PG_BT));  // j tiles per gate
+  const DropMasks dm{dp, rdp};
+  if (cell == 0)
+    rev ? launch_param_grad_drop<0, true>(grid, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, dm)
+        : launch_param_grad_drop<0, false>(grid, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, dm);
+  else if (cell == 1)
+    rev ? launch_param_grad_drop<1, true>(grid, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, dm)
+        : launch_param_grad_drop<1, false>(grid, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, dm);
+  else
+    rev ? launch_param_grad_drop<2, true>(grid, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, dm)
+        : launch_param_grad_drop<2, false>(grid, s, dg, hs, gates, x, gU, gW, gb, B, T, H, I, dm);
+  return (int)hipGetLastError();
+}
+
+int rnn_drop_x(const float* x, const float* dp, float* xm, int G, int B, int T, int I, hipStream_t s) {
+  const long n = (long)G * B * T * I;
+  if (n <= 0) return 0;
+  const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(rnn_drop_x_kernel, dim3(blocks), dim3(256), 0, s, x, dp, xm, G, B, T, I);
+  return (int)hipGetLastError();
+}
+
+int rnn_drop_dx(const float* t, const float* dp, float* dx, int G, int B, int T, int I, int accumulate, hipStream_t s) {
+  const long n = (long)B * T * I;
+  if (n <= 0) return 0;
+  const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(rnn_drop_dx_kernel, dim3(blocks), dim3(256), 0, s, t, dp, dx, G, B, T, I, accumulate);
   return (int)hipGetLastError();
 }
 
@@ -976,14 +1164,21 @@ int rnn_bwd(int cell, const float* dy, const float* U, const float* UT, const fl
 int rnn_fwd_dir(int cell, const RnnDir& d, int ndir, const float* x, int I, int B, int T, int H, int rs, int act,
                 int ract, hipStream_t s) {
   if (ndir < 1 || ndir > 2 || (ndir == 2 && !d.xw[0] != !d.xw[1])) return (int)hipErrorInvalidValue;
-  return d.mask ? launch_fwd_dir<true>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s)
-                : launch_fwd_dir<false>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s);
+  if (ndir == 2 && !d.rdp[0] != !d.rdp[1]) return (int)hipErrorInvalidValue;
+  if (d.rdp[0])
+    return d.mask ? launch_fwd_dir<true, true>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s)
+                  : launch_fwd_dir<false, true>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s);
+  return d.mask ? launch_fwd_dir<true, false>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s)
+                : launch_fwd_dir<false, false>(cell, d, ndir, x, I, B, T, H, rs, act, ract, s);
 }
 
 int rnn_bwd_dir(int cell, const RnnDir& d, int ndir, int B, int T, int H, int rs, int act, int ract, hipStream_t s) {
-  if (ndir < 1 || ndir > 2) return (int)hipErrorInvalidValue;
-  return d.mask ? launch_bwd_dir<true>(cell, d, ndir, B, T, H, rs, act, ract, s)
-                : launch_bwd_dir<false>(cell, d, ndir, B, T, H, rs, act, ract, s);
+  if (ndir < 1 || ndir > 2 || (ndir == 2 && !d.rdp[0] != !d.rdp[1])) return (int)hipErrorInvalidValue;
+  if (d.rdp[0])
+    return d.mask ? launch_bwd_dir<true, true>(cell, d, ndir, B, T, H, rs, act, ract, s)
+                  : launch_bwd_dir<false, true>(cell, d, ndir, B, T, H, rs, act, ract, s);
+  return d.mask ? launch_bwd_dir<true, false>(cell, d, ndir, B, T, H, rs, act, ract, s)
+                : launch_bwd_dir<false, false>(cell, d, ndir, B, T, H, rs, act, ract, s);
 }
 
 int bidir_merge(const float* a, const float* b, float* out, long n, float scale, hipStream_t s) {

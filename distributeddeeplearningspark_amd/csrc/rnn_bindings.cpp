@@ -71,8 +71,40 @@ const unsigned char* mask_ptr(const c10::optional<at::Tensor>& mask, const at::T
   return mask->data_ptr<unsigned char>();
 }
 
+// Dropout masks of a directed call (ddl_ops.h): per direction the input multipliers dp [G, B, I] and the recurrent
+// ones rdp [G, B, H], each kind given for every direction or for none.
+struct DropSet {
+  std::vector<at::Tensor> dp, rdp;  // empty: none
+  bool any() const { return !dp.empty() || !rdp.empty(); }
+};
+
+std::vector<at::Tensor> drop_list(const std::vector<c10::optional<at::Tensor>>& ms, const at::Tensor& x, int64_t G,
+                                  int64_t n, size_t nd, const char* who, const char* what) {
+  size_t given = 0;
+  for (const auto& m : ms) given += m.has_value();
+  if (!given) return {};
+  TORCH_CHECK(ms.size() == nd && given == nd, who, ": ", what, " for every direction or for none");
+  std::vector<at::Tensor> out;
+  for (const auto& m : ms) {
+    TORCH_CHECK(m->scalar_type() == at::kFloat && m->dim() == 3 && m->size(0) == G && m->size(1) == x.size(0) &&
+                    m->size(2) == n, who, ": ", what, " must be fp32 [G, B, ", n, "]");
+    TORCH_CHECK(m->is_contiguous() && m->device() == x.device(), who, ": ", what,
+                " must be contiguous and on the input's device");
+    out.push_back(*m);
+  }
+  return out;
+}
+
+DropSet drop_set(const std::vector<c10::optional<at::Tensor>>& dps, const std::vector<c10::optional<at::Tensor>>& rdps,
+                 const at::Tensor& x, int64_t G, int64_t H, size_t nd, const char* who) {
+  TORCH_CHECK(x.dim() == 3, who, ": x [B,T,I] fp32 on GPU");
+  return {drop_list(dps, x, G, x.size(2), nd, who, "dropout_mask"),
+          drop_list(rdps, x, G, H, nd, who, "recurrent_dropout_mask")};
+}
+
 py::tuple dir_fwd(int c, const at::Tensor& x, const std::vector<DirWeights>& w, const std::vector<int>& rev, bool rs,
-                  int merge, bool yproc, int64_t act, int64_t ract, const c10::optional<at::Tensor>& mask) {
+                  int merge, bool yproc, int64_t act, int64_t ract, const c10::optional<at::Tensor>& mask,
+                  const DropSet& drop = {}) {
   const int G = gates_of(c);
   const int nd = (int)w.size();
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
@@ -84,8 +116,23 @@ py::tuple dir_fwd(int c, const at::Tensor& x, const std::vector<DirWeights>& w, 
   auto opt = x.options();
   at::Tensor xw;
   const bool reg = rnn_reg_path(c, (int)H, (int)act, (int)ract);
-  if (!(reg && rnn_fuses_input((int)H, (int)I))) {  // one projection GEMM per direction
+  if (!drop.dp.empty()) {
+    // input dropout: gate g's column block of xw projects its own masked copy of x, all T steps at once
     xw = at::empty({nd, B * T, G * H}, opt);
+    at::Tensor xm = at::empty({G, B * T, I}, opt);
+    for (int d = 0; d < nd; ++d) {
+      int e = rnn_drop_x(xc.data_ptr<float>(), drop.dp[d].data_ptr<float>(), xm.data_ptr<float>(), G, (int)B, (int)T,
+                         (int)I, cur_stream());
+      TORCH_CHECK(e == 0, "rnn_drop_x launch failed: ", hipGetErrorString((hipError_t)e));
+      for (int g = 0; g < G; ++g) {
+        e = gemm_f32(xm.data_ptr<float>() + g * B * T * I, I, 1, w[d].W.data_ptr<float>() + g * H, G * H, 1,
+                     xw.data_ptr<float>() + d * B * T * G * H + g * H, G * H, (int)(B * T), (int)H, (int)I, 1.f, 0.f,
+                     w[d].b.defined() ? w[d].b.data_ptr<float>() + g * H : nullptr, 0, cur_stream());
+        TORCH_CHECK(e == 0, "gemm_f32 launch failed: ", hipGetErrorString((hipError_t)e));
+      }
+    }
+  } else if (!(reg && rnn_fuses_input((int)H, (int)I)) || drop.any()) {  // one projection GEMM per direction
+    xw = at::empty({nd, B * T, G * H}, opt);                             // (recurrent dropout: never fused)
     for (int d = 0; d < nd; ++d) {
       at::Tensor xwd = xw.select(0, d);
       f32mm(xc, I, 1, w[d].W, G * H, 1, xwd, G * H, B * T, G * H, I, 0.f,
@@ -112,6 +159,7 @@ py::tuple dir_fwd(int c, const at::Tensor& x, const std::vector<DirWeights>& w, 
     dr.rev[d] = rev[d];
     dr.yoff[d] = merge == 1 ? d * (int)H : 0;
     dr.yproc[d] = yproc ? 1 : 0;
+    dr.rdp[d] = drop.rdp.empty() ? nullptr : drop.rdp[d].data_ptr<float>();
   }
   dr.ldy = (int)Hy;
   dr.dscale = 1.f;
@@ -135,28 +183,33 @@ py::tuple dir_fwd(int c, const at::Tensor& x, const std::vector<DirWeights>& w, 
 // returned in fresh ones
 py::tuple dir_param_grads(int c, const at::Tensor& dg, const at::Tensor& hs, const at::Tensor& gates,
                           const at::Tensor& xc, bool has_b, int rev, const at::Tensor& gW, const at::Tensor& gU,
-                          const at::Tensor& gb, int64_t B, int64_t T, int64_t I, int64_t H) {
+                          const at::Tensor& gb, int64_t B, int64_t T, int64_t I, int64_t H,
+                          const float* dp = nullptr, const float* rdp = nullptr) {
   const int G = gates_of(c);
-  const bool tiles = c != 0 || (2 * H) % 64 == 0;
+  const bool dropm = dp || rdp;  // per-gate tiles with the masks on the A rows: every cell and width
+  const bool tiles = dropm || c != 0 || (2 * H) % 64 == 0;
+  auto param_grad = [&](float* pU, float* pW, float* pb) {
+    const int e = dropm ? rnn_param_grad_drop(c, dg.data_ptr<float>(), hs.data_ptr<float>(), gates.data_ptr<float>(),
+                                              xc.data_ptr<float>(), dp, rdp, pU, pW, pb, (int)B, (int)T, (int)H, (int)I,
+                                              cur_stream(), rev)
+                        : rnn_param_grad(c, dg.data_ptr<float>(), hs.data_ptr<float>(), gates.data_ptr<float>(),
+                                         xc.data_ptr<float>(), pU, pW, pb, (int)B, (int)T, (int)H, (int)I, cur_stream(),
+                                         rev);
+    TORCH_CHECK(e == 0, "rnn_param_grad launch failed: ", hipGetErrorString((hipError_t)e));
+  };
   if (tiles && gU.defined() && gW.defined() && gb.defined() == has_b) {
     for (const at::Tensor* t : {&gU, &gW})
       TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous(), "rnn_bwd: fp32 contiguous grad buffers");
     TORCH_CHECK(gU.numel() == H * G * H && gW.numel() == I * G * H, "rnn_bwd: grad buffer sizes");
     if (has_b) TORCH_CHECK(gb.scalar_type() == at::kFloat && gb.numel() == G * H, "rnn_bwd: bias grad buffer");
-    const int e = rnn_param_grad(c, dg.data_ptr<float>(), hs.data_ptr<float>(), gates.data_ptr<float>(),
-                                 xc.data_ptr<float>(), gU.data_ptr<float>(), gW.data_ptr<float>(),
-                                 has_b ? gb.data_ptr<float>() : nullptr, (int)B, (int)T, (int)H, (int)I, cur_stream(), rev);
-    TORCH_CHECK(e == 0, "rnn_param_grad launch failed: ", hipGetErrorString((hipError_t)e));
+    param_grad(gU.data_ptr<float>(), gW.data_ptr<float>(), has_b ? gb.data_ptr<float>() : nullptr);
     return py::make_tuple(py::none(), py::none(), py::none());
   }
   at::Tensor dW = at::zeros({I, G * H}, xc.options());
   at::Tensor dU = at::zeros({H, G * H}, xc.options());
   at::Tensor db = has_b ? at::zeros({G * H}, xc.options()) : at::Tensor();
   if (tiles) {
-    const int e = rnn_param_grad(c, dg.data_ptr<float>(), hs.data_ptr<float>(), gates.data_ptr<float>(),
-                                 xc.data_ptr<float>(), dU.data_ptr<float>(), dW.data_ptr<float>(),
-                                 has_b ? db.data_ptr<float>() : nullptr, (int)B, (int)T, (int)H, (int)I, cur_stream(), rev);
-    TORCH_CHECK(e == 0, "rnn_param_grad launch failed: ", hipGetErrorString((hipError_t)e));
+    param_grad(dU.data_ptr<float>(), dW.data_ptr<float>(), has_b ? db.data_ptr<float>() : nullptr);
   } else {
     // GRU with 2H not a multiple of 64 (as rnn_bwd_): h_{t-1} is slot t + rev of the saved sequence
     at::Tensor hp = hs.narrow(1, rev, T).contiguous().view({B * T, H});
@@ -180,7 +233,7 @@ py::tuple dir_param_grads(int c, const at::Tensor& dg, const at::Tensor& hs, con
 py::tuple dir_bwd(int c, const at::Tensor& dy, const at::Tensor& x, const std::vector<DirWeights>& w,
                   const std::vector<int>& rev, bool rs, int merge, bool yproc, const std::vector<at::Tensor>& saved,
                   const std::vector<DirWeights>& gr, bool need_dx, int64_t act, int64_t ract,
-                  const c10::optional<at::Tensor>& mask) {
+                  const c10::optional<at::Tensor>& mask, const DropSet& drop = {}) {
   const int G = gates_of(c);
   const int nd = (int)w.size();
   TORCH_CHECK(x.is_cuda() && x.dim() == 3, "rnn_bwd: x [B,T,I] on GPU");
@@ -220,6 +273,7 @@ py::tuple dir_bwd(int c, const at::Tensor& dy, const at::Tensor& x, const std::v
     dr.rev[d] = rev[d];
     dr.yoff[d] = merge == 1 ? d * (int)H : 0;
     dr.yproc[d] = yproc ? 1 : 0;
+    dr.rdp[d] = drop.rdp.empty() ? nullptr : drop.rdp[d].data_ptr<float>();
   }
   dr.ldy = (int)Hy;
   dr.dscale = merge == 3 ? 0.5f : 1.f;
@@ -229,55 +283,79 @@ py::tuple dir_bwd(int c, const at::Tensor& dy, const at::Tensor& x, const std::v
   py::object dx = py::none();
   if (need_dx) {  // dx[bt][i] = sum_d sum_j dg_d[bt][j] W_d[i][j]: the second direction accumulates
     at::Tensor dxt = at::empty({B * T, I}, x.options());
-    for (int d = 0; d < nd; ++d) f32mm(dgates.select(0, d), G * H, 1, w[d].W, 1, G * H, dxt, I, B * T, I, G * H, d ? 1.f : 0.f);
+    if (!drop.dp.empty()) {  // dx[bt] = sum_d sum_g (dg_{d,g}[bt] W_{d,g}^T) * dp_d[g][b]
+      at::Tensor tg = at::empty({G, B * T, I}, x.options());
+      for (int d = 0; d < nd; ++d) {
+        for (int g = 0; g < G; ++g) {
+          const int e2 = gemm_f32(dgates.data_ptr<float>() + d * B * T * G * H + g * H, G * H, 1,
+                                  w[d].W.data_ptr<float>() + g * H, 1, G * H, tg.data_ptr<float>() + g * B * T * I, I,
+                                  (int)(B * T), (int)I, (int)H, 1.f, 0.f, nullptr, 0, cur_stream());
+          TORCH_CHECK(e2 == 0, "gemm_f32 launch failed: ", hipGetErrorString((hipError_t)e2));
+        }
+        const int e3 = rnn_drop_dx(tg.data_ptr<float>(), drop.dp[d].data_ptr<float>(), dxt.data_ptr<float>(), G, (int)B,
+                                   (int)T, (int)I, d ? 1 : 0, cur_stream());
+        TORCH_CHECK(e3 == 0, "rnn_drop_dx launch failed: ", hipGetErrorString((hipError_t)e3));
+      }
+    } else {
+      for (int d = 0; d < nd; ++d) f32mm(dgates.select(0, d), G * H, 1, w[d].W, 1, G * H, dxt, I, B * T, I, G * H, d ? 1.f : 0.f);
+    }
     dx = py::cast(dxt.view({B, T, I}));
   }
   py::list pg;
   for (int d = 0; d < nd; ++d)
     pg.append(dir_param_grads(c, dgates.select(0, d), hs.select(0, d), gates.select(0, d), xc, w[d].b.defined(), rev[d],
-                              gr[d].W, gr[d].U, gr[d].b, B, T, I, H));
+                              gr[d].W, gr[d].U, gr[d].b, B, T, I, H,
+                              drop.dp.empty() ? nullptr : drop.dp[d].data_ptr<float>(),
+                              drop.rdp.empty() ? nullptr : drop.rdp[d].data_ptr<float>()));
   return py::make_tuple(dx, pg);
 }
 
 at::Tensor opt_tensor(const py::handle& o) { return o.is_none() ? at::Tensor() : o.cast<at::Tensor>(); }
 
 py::tuple birnn_fwd_(const std::string& cell, const at::Tensor& x, py::list Ws, py::list Us, py::list bs, bool rs,
-                     const std::string& merge, int64_t act, int64_t ract, c10::optional<at::Tensor> mask) {
+                     const std::string& merge, int64_t act, int64_t ract, c10::optional<at::Tensor> mask,
+                     std::vector<c10::optional<at::Tensor>> dps, std::vector<c10::optional<at::Tensor>> rdps) {
   const int c = cell_id(cell);
   TORCH_CHECK(Ws.size() == 2, "birnn_fwd: [forward, backward] weights");
-  return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), gates_of(c)), {0, 1}, rs, merge_id(merge), false, act, ract,
-                 mask);
+  std::vector<DirWeights> w = dir_weights(Ws, Us, bs, x.size(2), gates_of(c));
+  const DropSet drop = drop_set(dps, rdps, x, gates_of(c), w[0].U.size(0), 2, "birnn_fwd");
+  return dir_fwd(c, x, w, {0, 1}, rs, merge_id(merge), false, act, ract, mask, drop);
 }
 
 py::tuple birnn_bwd_(const std::string& cell, const at::Tensor& dy, const at::Tensor& x, py::list Ws, py::list Us,
                      py::list bs, bool rs, const std::string& merge, std::vector<at::Tensor> saved, py::list gWs,
                      py::list gUs, py::list gbs, bool need_dx, int64_t act, int64_t ract,
-                     c10::optional<at::Tensor> mask) {
+                     c10::optional<at::Tensor> mask, std::vector<c10::optional<at::Tensor>> dps,
+                     std::vector<c10::optional<at::Tensor>> rdps) {
   const int c = cell_id(cell);
   TORCH_CHECK(Ws.size() == 2 && gWs.size() == 2 && gUs.size() == 2 && gbs.size() == 2,
               "birnn_bwd: [forward, backward] weights and gradient buffers");
   std::vector<DirWeights> gr(2);
   for (int d = 0; d < 2; ++d) gr[d] = {opt_tensor(gWs[d]), opt_tensor(gUs[d]), opt_tensor(gbs[d])};
-  return dir_bwd(c, dy, x, dir_weights(Ws, Us, bs, x.size(2), gates_of(c)), {0, 1}, rs, merge_id(merge), false, saved,
-                 gr, need_dx, act, ract, mask);
+  std::vector<DirWeights> w = dir_weights(Ws, Us, bs, x.size(2), gates_of(c));
+  const DropSet drop = drop_set(dps, rdps, x, gates_of(c), w[0].U.size(0), 2, "birnn_bwd");
+  return dir_bwd(c, dy, x, w, {0, 1}, rs, merge_id(merge), false, saved, gr, need_dx, act, ract, mask, drop);
 }
 
 // reverse: the sequence is processed last-to-first (go_backwards).  y_input_order: a returned sequence (and its
 // gradient) is in input time order; default is Keras' processing order.  Both default to the forward layer.
 // mask: uint8 [B, T] step mask (1 = data); a masked layer runs the directed kernels, forward as one direction.
+// dropout_mask / recurrent_dropout_mask: fp32 [G, B, I] / [G, B, H] multipliers (ddl_ops.h); a call with either runs
+// the directed kernels too.
 py::tuple rnn_fwd_(const std::string& cell, const at::Tensor& x, const at::Tensor& W, const at::Tensor& U,
                    c10::optional<at::Tensor> b, bool rs, int64_t act, int64_t ract, bool reverse, bool y_input_order,
-                   c10::optional<at::Tensor> mask) {
+                   c10::optional<at::Tensor> mask, c10::optional<at::Tensor> dmask, c10::optional<at::Tensor> rmask) {
   const int c = cell_id(cell);
   const int G = gates_of(c);
-  if (reverse || mask) {
+  if (reverse || mask || dmask || rmask) {
     TORCH_CHECK(x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
     py::list Ws, Us, bs;
     Ws.append(W);
     Us.append(U);
     bs.append(b ? py::cast(*b) : py::none());
-    return dir_fwd(c, x, dir_weights(Ws, Us, bs, x.size(2), G), {reverse ? 1 : 0}, rs, 0, !y_input_order, act, ract,
-                   mask);
+    std::vector<DirWeights> w = dir_weights(Ws, Us, bs, x.size(2), G);
+    const DropSet drop = drop_set({dmask}, {rmask}, x, G, w[0].U.size(0), 1, "rnn_fwd");
+    return dir_fwd(c, x, w, {reverse ? 1 : 0}, rs, 0, !y_input_order, act, ract, mask, drop);
   }
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.dim() == 3, "rnn_fwd: x [B,T,I] fp32 on GPU");
   const int64_t B = x.size(0), T = x.size(1), I = x.size(2), H = U.size(0);
@@ -317,10 +395,10 @@ py::tuple rnn_bwd_(const std::string& cell, const at::Tensor& dy, const at::Tens
                    const at::Tensor& U, c10::optional<at::Tensor> b, bool rs, std::vector<at::Tensor> saved,
                    c10::optional<at::Tensor> gW, c10::optional<at::Tensor> gU, c10::optional<at::Tensor> gb,
                    bool need_dx, int64_t act, int64_t ract, bool reverse, bool y_input_order,
-                   c10::optional<at::Tensor> mask) {
+                   c10::optional<at::Tensor> mask, c10::optional<at::Tensor> dmask, c10::optional<at::Tensor> rmask) {
   const int c = cell_id(cell);
   const int G = gates_of(c);
-  if (reverse || mask) {
+  if (reverse || mask || dmask || rmask) {
     TORCH_CHECK(x.dim() == 3, "rnn_bwd: x [B,T,I] fp32 on GPU");
     py::list Ws, Us, bs;
     Ws.append(W);
@@ -328,8 +406,10 @@ py::tuple rnn_bwd_(const std::string& cell, const at::Tensor& dy, const at::Tens
     bs.append(b ? py::cast(*b) : py::none());
     std::vector<DirWeights> gr(1);
     gr[0] = {gW ? *gW : at::Tensor(), gU ? *gU : at::Tensor(), gb ? *gb : at::Tensor()};
-    py::tuple r = dir_bwd(c, dy, x, dir_weights(Ws, Us, bs, x.size(2), G), {reverse ? 1 : 0}, rs, 0, !y_input_order,
-                          saved, gr, need_dx, act, ract, mask);
+    std::vector<DirWeights> w = dir_weights(Ws, Us, bs, x.size(2), G);
+    const DropSet drop = drop_set({dmask}, {rmask}, x, G, w[0].U.size(0), 1, "rnn_bwd");
+    py::tuple r = dir_bwd(c, dy, x, w, {reverse ? 1 : 0}, rs, 0, !y_input_order, saved, gr, need_dx, act, ract, mask,
+                          drop);
     py::tuple pg = r[1].cast<py::list>()[0].cast<py::tuple>();
     return py::make_tuple(r[0], pg[0], pg[1], pg[2]);
   }
@@ -527,24 +607,29 @@ at::Tensor mask_from_ids_(const at::Tensor& ids) {
 }  // namespace
 
 void register_rnn(py::module& m) {
+  const std::vector<c10::optional<at::Tensor>> kNoDrop{c10::nullopt, c10::nullopt};  // [forward, backward]: none
   m.def("rnn_fwd", &rnn_fwd_, "persistent GRU/LSTM/SimpleRNN forward (fp32)", py::arg("cell"), py::arg("x"),
         py::arg("W"), py::arg("U"), py::arg("b"), py::arg("rs"), py::arg("act") = (int64_t)ACT_C_TANH,
         py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID, py::arg("reverse") = false, py::arg("y_input_order") = false,
-        py::arg("mask") = py::none());
+        py::arg("mask") = py::none(), py::arg("dropout_mask") = py::none(),
+        py::arg("recurrent_dropout_mask") = py::none());
   m.def("rnn_bwd", &rnn_bwd_, "persistent GRU/LSTM backward (fp32)", py::arg("cell"), py::arg("dy"), py::arg("x"),
         py::arg("W"), py::arg("U"), py::arg("b"), py::arg("rs"), py::arg("saved"), py::arg("gW") = py::none(),
         py::arg("gU") = py::none(), py::arg("gb") = py::none(), py::arg("need_dx") = true,
         py::arg("act") = (int64_t)ACT_C_TANH, py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID,
-        py::arg("reverse") = false, py::arg("y_input_order") = false, py::arg("mask") = py::none());
+        py::arg("reverse") = false, py::arg("y_input_order") = false, py::arg("mask") = py::none(),
+        py::arg("dropout_mask") = py::none(), py::arg("recurrent_dropout_mask") = py::none());
   m.def("birnn_fwd", &birnn_fwd_, "Bidirectional GRU/LSTM/SimpleRNN forward: both directions in one recurrence launch",
         py::arg("cell"), py::arg("x"), py::arg("Ws"), py::arg("Us"), py::arg("bs"), py::arg("rs"),
         py::arg("merge") = "concat", py::arg("act") = (int64_t)ACT_C_TANH,
-        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID, py::arg("mask") = py::none());
+        py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID, py::arg("mask") = py::none(),
+        py::arg("dropout_masks") = kNoDrop, py::arg("recurrent_dropout_masks") = kNoDrop);
   m.def("birnn_bwd", &birnn_bwd_, "Bidirectional backward: one recurrence launch, parameter gradients per direction",
         py::arg("cell"), py::arg("dy"), py::arg("x"), py::arg("Ws"), py::arg("Us"), py::arg("bs"), py::arg("rs"),
         py::arg("merge"), py::arg("saved"), py::arg("gWs"), py::arg("gUs"), py::arg("gbs"), py::arg("need_dx") = true,
         py::arg("act") = (int64_t)ACT_C_TANH, py::arg("ract") = (int64_t)ACT_C_HARD_SIGMOID,
-        py::arg("mask") = py::none());
+        py::arg("mask") = py::none(), py::arg("dropout_masks") = kNoDrop,
+        py::arg("recurrent_dropout_masks") = kNoDrop);
   m.def("mask_from_features", &mask_from_features_, "step mask any_f(x != mask_value) of x [B,T,F]; y = x * mask",
         py::arg("x"), py::arg("mask_value"), py::arg("apply"));
   m.def("mask_apply", &mask_apply_, "out = in * mask[..., None] (the Masking gradient)", py::arg("x"), py::arg("mask"));

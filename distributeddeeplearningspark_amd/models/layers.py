@@ -366,8 +366,14 @@ class _Recurrent(Layer):
     takes_mask = True  # skips masked steps; passes the mask on with return_sequences, else consumes it
 
     def __init__(self, units, activation="tanh", recurrent_activation="hard_sigmoid", return_sequences=False,
-                 use_bias=True, unit_forget_bias=True, go_backwards=False, **kw):
+                 use_bias=True, unit_forget_bias=True, go_backwards=False, dropout=0.0, recurrent_dropout=0.0, **kw):
         super().__init__(**kw)
+        for what, rate in (("dropout", dropout), ("recurrent_dropout", recurrent_dropout)):
+            if not 0.0 <= float(rate) < 1.0:
+                raise ValueError(f"{type(self).__name__}: {what} must be in [0, 1), got {rate}")
+        # Keras (implementation=1): per-gate masks on the input / the recurrent state, drawn once per batch and
+        # held over all time steps; active in training only
+        self.dropout, self.recurrent_dropout = float(dropout), float(recurrent_dropout)
         self.units = int(units)
         self.activation = activation
         self.recurrent_activation = recurrent_activation
@@ -404,18 +410,34 @@ class _Recurrent(Layer):
     def compute_output_shape(self, s):
         return (s[0], self.units) if self.return_sequences else (self.units,)
 
+    @property
+    def uses_dropout(self):
+        return self.dropout > 0 or self.recurrent_dropout > 0
+
+    def draw_dropout_masks(self, x, training):
+        """(dropout_mask | None, recurrent_dropout_mask | None) of one forward call over x [B, T, I]."""
+        if not training:
+            return None, None
+        B, G = x.shape[0], self.n_gates
+        dp = rnn_ops.dropout_masks(G, B, x.shape[2], self.dropout, x.device) if self.dropout > 0 else None
+        rdp = (rnn_ops.dropout_masks(G, B, self.units, self.recurrent_dropout, x.device)
+               if self.recurrent_dropout > 0 else None)
+        return dp, rdp
+
     def call(self, x, training=False, mask=None):
+        dp, rdp = self.draw_dropout_masks(x, training)
         return rnn_ops.recurrent(
             self.cell, x, self.kernel.data, self.recurrent_kernel.data, None if self.bias is None else self.bias.data,
             grads=(self.kernel.grad, self.recurrent_kernel.grad, None if self.bias is None else self.bias.grad),
             return_sequences=self.return_sequences, activation=self.activation,
             recurrent_activation=self.recurrent_activation, on_grad=self.grad_hook, go_backwards=self.go_backwards,
-            mask=mask)
+            mask=mask, dropout_mask=dp, recurrent_dropout_mask=rdp)
 
     def get_config(self):
         return {**super().get_config(), "units": self.units, "activation": self.activation,
                 "recurrent_activation": self.recurrent_activation, "return_sequences": self.return_sequences,
-                "use_bias": self.use_bias, "go_backwards": self.go_backwards}
+                "use_bias": self.use_bias, "go_backwards": self.go_backwards, "dropout": self.dropout,
+                "recurrent_dropout": self.recurrent_dropout}
 
 
 class GRU(_Recurrent):
@@ -448,6 +470,10 @@ class Bidirectional(Layer):
     names ``<wrapper>/forward_<layer>/...`` and ``<wrapper>/backward_<layer>/...``."""
 
     takes_mask = True  # both directions read the same mask
+
+    @property
+    def uses_dropout(self):
+        return self.forward_layer.uses_dropout
 
     def __init__(self, layer, merge_mode="concat", **kw):
         if isinstance(layer, dict):  # a Keras config ({"class_name", "config"})
@@ -504,9 +530,11 @@ class Bidirectional(Layer):
             return yf + yb if self.merge_mode == "sum" else (yf + yb) * 0.5
         wts = lambda l: (l.kernel.data, l.recurrent_kernel.data, None if l.bias is None else l.bias.data)
         grads = lambda l: (l.kernel.grad, l.recurrent_kernel.grad, None if l.bias is None else l.bias.grad)
+        (dpf, rdpf), (dpb, rdpb) = f.draw_dropout_masks(x, training), b.draw_dropout_masks(x, training)  # independent
         y = rnn_ops.bidirectional(f.cell, x, wts(f), wts(b), grads=(grads(f), grads(b)), merge_mode=self.merge_mode,
                                   return_sequences=f.return_sequences, activation=f.activation,
-                                  recurrent_activation=f.recurrent_activation, on_grad=self._fire_hooks, mask=mask)
+                                  recurrent_activation=f.recurrent_activation, on_grad=self._fire_hooks, mask=mask,
+                                  dropout_mask=(dpf, dpb), recurrent_dropout_mask=(rdpf, rdpb))
         return y
 
     def get_config(self):

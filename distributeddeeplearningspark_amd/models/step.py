@@ -54,7 +54,8 @@ def graphs_enabled() -> bool:
 def _uses_dropout(model) -> bool:
     from .layers import Dropout
 
-    return any(isinstance(l, Dropout) and l.rate > 0 for l in model.all_layers())
+    # a recurrent layer (or a Bidirectional of one) with dropout / recurrent_dropout draws its masks with the same kernel
+    return any((isinstance(l, Dropout) and l.rate > 0) or getattr(l, "uses_dropout", False) for l in model.all_layers())
 
 
 class CompiledTrainStep:

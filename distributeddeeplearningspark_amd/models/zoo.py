@@ -61,21 +61,24 @@ def bilstm_regressor(units: int = 128, seq_len: int = 25, features: int = 1, out
     return m
 
 
-def text_lstm_classifier(vocab_size: int, maxlen: int, embed_dim: int = 32, units: int = 64) -> Sequential:
-    """The classic Keras text model over zero-padded id sequences: id 0 is padding and its steps are skipped."""
+def text_lstm_classifier(vocab_size: int, maxlen: int, embed_dim: int = 32, units: int = 64, dropout: float = 0.0,
+                         recurrent_dropout: float = 0.0) -> Sequential:
+    """The classic Keras text model over zero-padded id sequences: id 0 is padding and its steps are skipped.
+    ``dropout`` / ``recurrent_dropout`` are the LSTM's (Keras' example uses 0.2 for both)."""
     m = Sequential()
     m.add(Embedding(vocab_size, embed_dim, mask_zero=True, input_shape=(maxlen,)))
-    m.add(LSTM(units))
+    m.add(LSTM(units, dropout=dropout, recurrent_dropout=recurrent_dropout))
     m.add(Dense(1, activation="sigmoid"))
     return m
 
 
 def masked_gru_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outputs: int = 1,
-                         mask_value: float = 0.0) -> Sequential:
+                         mask_value: float = 0.0, dropout: float = 0.0,
+                         recurrent_dropout: float = 0.0) -> Sequential:
     """``gru_regressor`` over ragged series padded with ``mask_value`` to ``seq_len`` steps."""
     m = Sequential()
     m.add(Masking(mask_value=mask_value, input_shape=(seq_len, features)))
-    m.add(GRU(units))
+    m.add(GRU(units, dropout=dropout, recurrent_dropout=recurrent_dropout))
     m.add(Dense(outputs, activation="linear"))
     return m
 

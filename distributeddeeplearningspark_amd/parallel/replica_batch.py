@@ -79,6 +79,8 @@ def why_not(group) -> str | None:
         rnn, dense = ls
         if rnn.go_backwards:
             return "go_backwards recurrent layer (the batched kernels run forward only)"
+        if rnn.uses_dropout:
+            return "recurrent dropout (the batched kernels take no dropout masks)"
         if (rnn.return_sequences or not rnn.use_bias or rnn.activation != "tanh"
                 or rnn.recurrent_activation != "hard_sigmoid" or not rnn.trainable or not dense.trainable):
             return "recurrent layer outside the fused cell (return_sequences / no bias / activations / frozen)"
