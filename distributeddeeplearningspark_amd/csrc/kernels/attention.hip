@@ -306,7 +306,7 @@ __global__ __launch_bounds__(THREADS, MINB) void attn_fwd_kernel(const AttnParam
 
 // ================================================================ backward: dK, dV
 // MINB = resident blocks per CU the register allocation is capped for: 1 (no spills) or 2 (twice the
-// waves to hide latency); picked at launch by DDL_ATTN_DKDV_OCC (default 2).  Dropout is a template
+// waves to hide latency); the launcher instantiates 2, a compile-time constant.  Dropout is a template
 // parameter; key padding is a second instantiation of the q-tile loop, chosen per workgroup (only
 // workgroups whose 128 keys straddle the padding pay for the mask).  A lane holds P[i][j] for four
 // consecutive queries i of one key j, and the dropout bytes of a (query, 4-key group) come from one

@@ -44,12 +44,17 @@ AttnParams make_params(const at::Tensor& qkv, int64_t B, int64_t S, int64_t H, i
   CK(ld % 8 == 0 && q_off % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0, "attn: 16-B aligned rows/offsets");
   CK(std::max({q_off, k_off, v_off}) + H * 64 <= qkv.size(1), "attn: head columns exceed qkv width");
   CK(((uintptr_t)qkv.data_ptr() % 16) == 0, "attn: qkv 16-B aligned");
+  // every pointer below goes to the kernels as is: a host tensor would hand them a host address
+  CK(o.is_cuda() && o.device() == qkv.device(), "attn: o must be a GPU tensor on qkv's device");
+  CK(lse.is_cuda() && lse.device() == qkv.device(), "attn: lse must be a GPU tensor on qkv's device");
   CK(o.scalar_type() == at::kBFloat16 && o.dim() == 2 && o.stride(1) == 1 && o.size(0) == B * S &&
          o.size(1) >= H * 64 && o.stride(0) % 8 == 0,
      "attn: o [tokens, >=H*64] bf16");
+  CK(((uintptr_t)o.data_ptr() % 16) == 0, "attn: o 16-B aligned");  // the dQ kernel reads it in 16-B fragments
   F32(lse);
   CK(lse.numel() == B * H * S, "attn: lse [B,H,S]");
   if (lens) {
+    CK(lens->is_cuda() && lens->device() == qkv.device(), "attn: lens must be a GPU tensor on qkv's device");
     CK(lens->scalar_type() == at::kInt && lens->is_contiguous() && lens->numel() == B, "attn: lens int32 [B]");
   }
   CK(drop_p >= 0 && drop_p < 1, "attn: dropout p in [0,1)");
@@ -88,9 +93,13 @@ void attn_bwd_(const at::Tensor& qkv, int64_t B, int64_t S, int64_t H, int64_t q
                const at::Tensor& o, const at::Tensor& lse, c10::optional<at::Tensor> lens, double scale, double drop_p,
                int64_t seed, const at::Tensor& dout, const at::Tensor& dvec, const at::Tensor& dqkv) {
   AttnParams p = make_params(qkv, B, S, H, q_off, k_off, v_off, o, lse, lens, scale, drop_p, seed);
+  CK(dout.is_cuda() && dout.device() == qkv.device(), "attn_bwd: dout must be a GPU tensor on qkv's device");
+  CK(dvec.is_cuda() && dvec.device() == qkv.device(), "attn_bwd: dvec must be a GPU tensor on qkv's device");
+  CK(dqkv.is_cuda() && dqkv.device() == qkv.device(), "attn_bwd: dqkv must be a GPU tensor on qkv's device");
   CK(dout.scalar_type() == at::kBFloat16 && dout.dim() == 2 && dout.stride(1) == 1 && dout.size(0) == B * S &&
          dout.stride(0) % 8 == 0,
      "attn_bwd: dout [tokens, ld] bf16");
+  CK(dout.size(1) >= H * 64 && ((uintptr_t)dout.data_ptr() % 16) == 0, "attn_bwd: dout >= H*64 columns, 16-B aligned");
   F32(dvec);
   CK(dvec.numel() == B * H * S, "attn_bwd: dvec [B,H,S]");
   CK(dqkv.scalar_type() == at::kBFloat16 && dqkv.dim() == 2 && dqkv.stride(1) == 1 && dqkv.size(0) == B * S &&

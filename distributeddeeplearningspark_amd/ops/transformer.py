@@ -169,7 +169,8 @@ def attention(qkv, B, S, H, *, q_off=None, k_off=None, v_off=None, lens=None, sc
     offs = (0 if q_off is None else q_off, HD if k_off is None else k_off, 2 * HD if v_off is None else v_off)
     scale = 1.0 / math.sqrt(64) if scale is None else scale
     if lens is not None:
-        lens = lens.to(torch.int32).contiguous()
+        # the kernels read lens on the device: a host tensor would hand them a host pointer
+        lens = lens.to(device=qkv.device, dtype=torch.int32).contiguous()
     return _AttentionFn.apply(qkv, (B, S, H, offs, lens, float(scale), float(drop_p), int(seed)))
 
 
