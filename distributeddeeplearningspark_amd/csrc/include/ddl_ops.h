@@ -109,6 +109,17 @@ int mse_fwd_bwd(const float* pred, const float* target, long n, float* loss, flo
 // Keras CE on probabilities: loss_rows[b] = -sum y log clip(p), dp = -scale * y / p inside the clip range
 int prob_xent(const float* p, const int64_t* labels, const float* target, float* loss_rows, float* dp, int B, int K,
               float eps, float scale, int ignore_index, hipStream_t s);
+// Masked per-time-step losses over rows r = b * T + t (fp32; mask uint8 [R] or nullptr = every step counts):
+// inv[0] = 1 / max(1, #mask != 0)
+int mask_count_inv(const uint8_t* mask, long n, float* inv, hipStream_t s);
+// loss_rows[r] = CE_r (0 at masked rows), dlogits[r] = (softmax_r - target_r) * inv (zeros at masked rows);
+// inv = inv_dev[0] or inv_host; labels int64 [R] OR target_probs [R, K]
+int temporal_xent(const float* logits, const int64_t* labels, const float* target_probs, const uint8_t* mask,
+                  const float* inv_dev, float inv_host, float* loss_rows, float* dlogits, long R, int K, hipStream_t s);
+// loss[0] = sum_r mask[r] * mean_F(err_r) / max(1, sum mask), err = squared (mae = 0) or absolute error; grad in
+// the same launch (zeros at masked rows)
+int temporal_reg(const float* pred, const float* target, const uint8_t* mask, long R, int F, int mae, float* loss,
+                 float* grad, hipStream_t s);
 
 // ---------------- elementwise ----------------
 int cast_f32_bf16(const float* x, void* y, long n, hipStream_t s);

@@ -338,4 +338,148 @@ int mse_fwd_bwd(const float* pred, const float* target, long n, float* loss, flo
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Masked per-time-step losses (Keras weighted_masked_objective: sum(score * mask) / sum(mask)) of a
+// [B, T, .] output, rows r = b * T + t, mask uint8 [B * T] (nullptr: every step counts), fp32 only.
+// A masked row is SELECTED out: nothing at it is read (NaN logits, out-of-range labels), its gradient
+// row is written as zeros (the Dense backward behind the loss reads every row).
+
+// inv[0] = 1 / max(1, #steps with mask != 0): the normaliser, counted on the device (no host sync)
+__global__ __launch_bounds__(1024) void mask_count_inv_kernel(const uint8_t* __restrict__ mask, long n,
+                                                              float* __restrict__ inv) {
+  __shared__ float part[16];
+  float c = 0.f;
+  for (long i = threadIdx.x; i < n; i += 1024) c += mask[i] ? 1.f : 0.f;
+  c = warp_sum(c);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int w = 0; w < 16; ++w) t += part[w];
+    inv[0] = 1.f / fmaxf(t, 1.f);
+  }
+}
+
+int mask_count_inv(const uint8_t* mask, long n, float* inv, hipStream_t s) {
+  hipLaunchKernelGGL(mask_count_inv_kernel, dim3(1), dim3(1024), 0, s, mask, n, inv);
+  return (int)hipGetLastError();
+}
+
+// Temporal softmax cross-entropy, loss terms and gradient in one sweep: a wave per row (tagging heads are
+// narrow, K from 2 to a few hundred, over thousands of rows), 4 rows per workgroup, lanes over the classes.
+// loss_rows[r] = CE_r (0 at a masked row; rows_sum_scaled applies inv), dlogits[r] = (softmax_r - target_r) * inv.
+// inv = inv_dev[0] (mask_count_inv) or inv_host (no mask: 1 / R).  A class label outside [0, K) at a step that
+// counts gives that row no loss and no gradient (it still counts in the normaliser).
+__global__ __launch_bounds__(256) void temporal_xent_kernel(const float* __restrict__ logits,
+                                                            const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ tprob,
+                                                            const uint8_t* __restrict__ mask,
+                                                            const float* __restrict__ inv_dev, float inv_host,
+                                                            float* __restrict__ loss_rows, float* __restrict__ dlogits,
+                                                            long R, int K) {
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= R) return;
+  float* d = dlogits + r * K;
+  bool on = mask == nullptr || mask[r] != 0;
+  long lab = -1;
+  if (on && labels) {
+    lab = labels[r];
+    on = lab >= 0 && lab < K;
+  }
+  if (!on) {
+    for (int k = lane; k < K; k += 64) d[k] = 0.f;
+    if (lane == 0) loss_rows[r] = 0.f;
+    return;
+  }
+  const float inv = inv_dev ? inv_dev[0] : inv_host;
+  const float* x = logits + r * K;
+  float m = -INFINITY;
+  for (int k = lane; k < K; k += 64) m = fmaxf(m, x[k]);
+  m = warp_max(m);
+  float se = 0.f;
+  for (int k = lane; k < K; k += 64) se += expf(x[k] - m);
+  se = warp_sum(se);
+  const float lse = m + logf(se);
+  float lpart = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const float xv = x[k];
+    const float t = tprob ? tprob[r * K + k] : (k == lab ? 1.f : 0.f);
+    lpart += t * (lse - xv);
+    d[k] = (expf(xv - lse) - t) * inv;
+  }
+  lpart = warp_sum(lpart);
+  if (lane == 0) loss_rows[r] = lpart;
+}
+
+int temporal_xent(const float* logits, const int64_t* labels, const float* target_probs, const uint8_t* mask,
+                  const float* inv_dev, float inv_host, float* loss_rows, float* dlogits, long R, int K,
+                  hipStream_t s) {
+  if (R <= 0) return 0;
+  if ((labels == nullptr) == (target_probs == nullptr) || (R + 3) / 4 > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(temporal_xent_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, logits, labels, target_probs,
+                     mask, inv_dev, inv_host, loss_rows, dlogits, R, K);
+  return (int)hipGetLastError();
+}
+
+// Temporal MSE (MAE = false) / MAE: score_r = mean over F of (p - t)^2 / |p - t|, loss = inv * sum of the
+// scores at the steps that count, grad = 2 (p - t) * inv / F or sign(p - t) * inv / F (sign(0) = 0).
+// One 1024-thread workgroup (these heads are small) counts the mask, then sweeps: one launch in all.
+template <bool MAE>
+__global__ __launch_bounds__(1024) void temporal_reg_kernel(const float* __restrict__ p, const float* __restrict__ t,
+                                                            const uint8_t* __restrict__ mask, long R, int F,
+                                                            float* __restrict__ loss, float* __restrict__ grad) {
+  __shared__ float part[16];
+  __shared__ float inv_sh;
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float inv = 1.f / (float)R;
+  if (mask) {
+    float c = 0.f;
+    for (long r = threadIdx.x; r < R; r += 1024) c += mask[r] ? 1.f : 0.f;
+    c = warp_sum(c);
+    if (lane == 0) part[wid] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float n = 0.f;
+      for (int w = 0; w < 16; ++w) n += part[w];
+      inv_sh = 1.f / fmaxf(n, 1.f);
+    }
+    __syncthreads();
+    inv = inv_sh;
+  }
+  const float gs = inv / (float)F;
+  const long n = R * F;
+  float acc = 0.f;
+  for (long i = threadIdx.x; i < n; i += 1024) {
+    if (mask && !mask[i / F]) {
+      grad[i] = 0.f;
+      continue;
+    }
+    const float d = p[i] - t[i];
+    if constexpr (MAE) {
+      acc += fabsf(d);
+      grad[i] = d > 0.f ? gs : (d < 0.f ? -gs : 0.f);
+    } else {
+      acc += d * d;
+      grad[i] = 2.f * d * gs;
+    }
+  }
+  acc = warp_sum(acc);
+  if (lane == 0) part[wid] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int w = 0; w < 16; ++w) s += part[w];
+    loss[0] = s * gs;
+  }
+}
+
+int temporal_reg(const float* pred, const float* target, const uint8_t* mask, long R, int F, int mae, float* loss,
+                 float* grad, hipStream_t s) {
+  if (R <= 0 || F <= 0) return (int)hipErrorInvalidValue;
+  if (mae) hipLaunchKernelGGL(temporal_reg_kernel<true>, dim3(1), dim3(1024), 0, s, pred, target, mask, R, F, loss, grad);
+  else hipLaunchKernelGGL(temporal_reg_kernel<false>, dim3(1), dim3(1024), 0, s, pred, target, mask, R, F, loss, grad);
+  return (int)hipGetLastError();
+}
+
 }  // namespace ddl

@@ -729,6 +729,44 @@ void mse_fwd_bwd_(const at::Tensor& pred, const at::Tensor& target, const at::Te
   HIP_OK(mse_fwd_bwd(pred.data_ptr<float>(), target.data_ptr<float>(), pred.numel(), loss.data_ptr<float>(),
                      grad.data_ptr<float>(), cur_stream()));
 }
+void mask_count_inv_(const at::Tensor& mask, const at::Tensor& inv) {
+  GPU(mask); GPU(inv); F32(inv);
+  CK(mask.scalar_type() == at::kByte && mask.is_contiguous() && inv.numel() == 1, "mask_count_inv: uint8 mask, inv [1]");
+  at::DeviceGuard g(mask.device());
+  HIP_OK(mask_count_inv(mask.data_ptr<uint8_t>(), mask.numel(), inv.data_ptr<float>(), cur_stream()));
+}
+void temporal_xent_(const at::Tensor& logits, c10::optional<at::Tensor> labels, c10::optional<at::Tensor> probs,
+                    c10::optional<at::Tensor> mask, c10::optional<at::Tensor> inv, double inv_host,
+                    const at::Tensor& loss_rows, const at::Tensor& dlogits) {
+  GPU(logits); F32(logits); GPU(loss_rows); F32(loss_rows); GPU(dlogits); F32(dlogits);
+  CK(logits.dim() == 2 && dlogits.sizes() == logits.sizes() && loss_rows.numel() == logits.size(0),
+     "temporal_xent: logits [R, K], dlogits [R, K], loss_rows [R]");
+  const int64_t R = logits.size(0), K = logits.size(1);
+  CK(K >= 1 && K <= INT32_MAX, "temporal_xent: K");
+  CK(labels.has_value() != probs.has_value(), "temporal_xent: labels OR probs");
+  if (labels) CK(labels->is_cuda() && labels->scalar_type() == at::kLong && labels->is_contiguous() && labels->numel() == R,
+                 "temporal_xent: int64 labels [R]");
+  if (probs) { GPU(*probs); F32(*probs); CK(probs->numel() == R * K, "temporal_xent: probs [R, K]"); }
+  if (mask) CK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() && mask->numel() == R,
+               "temporal_xent: uint8 mask [R]");
+  if (inv) { GPU(*inv); F32(*inv); CK(inv->numel() == 1, "temporal_xent: inv [1]"); }
+  at::DeviceGuard g(logits.device());
+  HIP_OK(temporal_xent(logits.data_ptr<float>(), labels ? labels->data_ptr<int64_t>() : nullptr, optr<const float>(probs),
+                       optr<const uint8_t>(mask), optr<const float>(inv), (float)inv_host, loss_rows.data_ptr<float>(),
+                       dlogits.data_ptr<float>(), (long)R, (int)K, cur_stream()));
+}
+void temporal_reg_(const at::Tensor& pred, const at::Tensor& target, c10::optional<at::Tensor> mask, bool mae,
+                   const at::Tensor& loss, const at::Tensor& grad) {
+  GPU(pred); F32(pred); GPU(target); F32(target); GPU(loss); F32(loss); GPU(grad); F32(grad);
+  CK(pred.dim() == 2 && pred.numel() > 0 && target.numel() == pred.numel() && grad.numel() == pred.numel() &&
+         loss.numel() == 1, "temporal_reg: pred / target / grad [R, F], loss [1]");
+  CK(pred.size(1) <= INT32_MAX, "temporal_reg: F");
+  if (mask) CK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() && mask->numel() == pred.size(0),
+               "temporal_reg: uint8 mask [R]");
+  at::DeviceGuard g(pred.device());
+  HIP_OK(temporal_reg(pred.data_ptr<float>(), target.data_ptr<float>(), optr<const uint8_t>(mask), (long)pred.size(0),
+                      (int)pred.size(1), mae ? 1 : 0, loss.data_ptr<float>(), grad.data_ptr<float>(), cur_stream()));
+}
 void etl_minmax_(const at::Tensor& x, const at::Tensor& y, double o_min, double scale, double n_min) {
   CK(x.is_cuda() && x.scalar_type() == at::kDouble && y.scalar_type() == at::kDouble && x.is_contiguous() &&
          y.is_contiguous() && x.numel() == y.numel(), "etl_minmax: contiguous fp64 x / y of equal size");
@@ -848,6 +886,9 @@ void register_ops(py::module& m) {
   m.def("step_tick", &step_tick_);
   m.def("mse_fwd_bwd", &mse_fwd_bwd_);
   m.def("prob_xent", &prob_xent_);
+  m.def("mask_count_inv", &mask_count_inv_);
+  m.def("temporal_xent", &temporal_xent_);
+  m.def("temporal_reg", &temporal_reg_);
   m.def("slab_reduce", &slab_reduce_);
   m.def("commit_delta", &commit_delta_);
   m.def("commit_apply", &commit_apply_);

@@ -207,6 +207,8 @@ class Model(Layer):
     """A trainable network: owns the parameter arena, optimizer and loss."""
 
     _masked = False  # True once Sequential.build_model() finds a layer that produces a step mask
+    _temporal_head = None  # the TimeDistributed head of a per-time-step Sequential (_find_temporal_head)
+    _output_masked = False  # True when a step mask reaches the output of such a model and weights its loss
 
     def __init__(self, name=None, **kw):
         super().__init__(name=name, **kw)
@@ -349,6 +351,8 @@ class Model(Layer):
         name = self.loss
         if callable(name):
             return name(self.forward(x, training), y)
+        if self._temporal_head is not None:
+            return self._temporal_loss(x, y, training)
         if name in ("categorical_crossentropy", "sparse_categorical_crossentropy") and self.ends_with_softmax():
             logits = self.forward(x, training, logits=True)
             logits = logits.reshape(logits.shape[0], -1)
@@ -554,26 +558,45 @@ class Sequential(Model):
         for l in self.layers:
             shape = l.ensure_built(shape)
         self.output_shape = tuple(shape)
+        self._temporal_head = self._find_temporal_head()
         self._masked = self._check_mask_flow()
         self.built = True
 
+    def _find_temporal_head(self):
+        """The ``TimeDistributed`` layer that makes this a per-time-step model, or None: the last layer with
+        weights, with nothing but ``Activation`` / ``Dropout`` layers behind it.  It is the one switch for the
+        temporal losses (``compute_loss``) and for a step mask that may reach the output."""
+        from .layers import Activation, Dropout, TimeDistributed
+
+        for l in reversed(self.layers):
+            if isinstance(l, TimeDistributed):
+                return l
+            if not isinstance(l, (Activation, Dropout)):
+                return None
+        return None
+
     def _check_mask_flow(self) -> bool:
         """Static mask propagation: True when some layer produces a step mask.  A mask may only reach layers that
-        pass it on or consume it, and must be consumed (a recurrent layer returning its last state) before the
-        output: Keras would weight the loss per time step there, which this loss layer does not do."""
+        pass it on or consume it.  It must be consumed (a recurrent layer returning its last state) before the
+        output, unless the model has a temporal head (``_find_temporal_head``): then the mask in flight at the
+        output weights the loss per time step (``_output_masked``)."""
+        self._output_masked = False
         carried, any_mask = None, False  # the producer of the mask in flight
         for l in self.layers:
             if carried is not None and not (l.takes_mask or l.passes_mask):
                 raise ValueError(f"{type(l).__name__} layer {l.name!r} cannot receive the step mask produced by "
-                                 f"{carried.name!r}: only Dropout, Activation, Dense, recurrent and Bidirectional "
-                                 "layers take one")
+                                 f"{carried.name!r}: only Dropout, Activation, Dense, TimeDistributed, recurrent and "
+                                 "Bidirectional layers take one")
             if l.produces_mask:
                 carried, any_mask = l, True
             elif carried is not None and l.takes_mask and not l.return_sequences:
                 carried = None
         if carried is not None:
-            raise ValueError(f"the step mask produced by {carried.name!r} reaches the model output: masked losses are "
-                             "not supported (end the masked part with a recurrent layer that returns its last state)")
+            if self._temporal_head is None:
+                raise ValueError(f"the step mask produced by {carried.name!r} reaches the model output: masked losses "
+                                 "are supported on a TimeDistributed(Dense) head only (end the masked part with a "
+                                 "recurrent layer that returns its last state, or the model with TimeDistributed)")
+            self._output_masked = True
         return any_mask
 
     def ends_with_softmax(self) -> bool:
@@ -641,12 +664,45 @@ class Sequential(Model):
             i += 1
         return x
 
-    def _forward_masked(self, x, training, logits):
+    _TEMPORAL_LOSSES = ("categorical_crossentropy", "sparse_categorical_crossentropy", "mean_squared_error",
+                        "mean_absolute_error")
+
+    def _temporal_loss(self, x, y, training):
+        """``compute_loss`` of a model with a temporal head: the loss of every time step of the ``[B, T, K]``
+        output, averaged over the steps the mask at the output keeps (all of them without one): Keras 2's
+        masked objective, ``ops/loss.py``.  Cross-entropy is softmax over K per step, fused with the loss."""
+        from ..ops import loss as L
+
+        name = self.loss
+        xent = name in ("categorical_crossentropy", "sparse_categorical_crossentropy")
+        if name not in self._TEMPORAL_LOSSES or (xent and not self.ends_with_softmax()):
+            raise ValueError(f"loss {name!r} is not supported on a TimeDistributed head"
+                             + (" that does not end with softmax" if xent else "")
+                             + f" (supported: {', '.join(self._TEMPORAL_LOSSES)}; the cross-entropies need a softmax "
+                             "on the wrapped Dense or a final Activation('softmax'))")
+        if self._masked:
+            out, mask = self._forward_masked(x, training, xent, return_mask=True)
+        else:
+            out, mask = self.forward(x, training, logits=xent), None
+        if out.dim() != 3:
+            raise ValueError(f"a TimeDistributed head gives a [B, T, K] output, got {tuple(out.shape)}")
+        B, T, K = out.shape
+        if xent:
+            if name == "sparse_categorical_crossentropy" or not y.is_floating_point():
+                return L.temporal_softmax_cross_entropy(out, labels=y.reshape(B, T).long(), mask=mask)
+            return L.temporal_softmax_cross_entropy(out, probs=y.float().reshape(B, T, K), mask=mask)
+        yy = y.float().reshape(B, T, K)
+        if name == "mean_squared_error":
+            return L.temporal_mean_squared_error(out, yy, mask=mask)
+        return L.temporal_mean_absolute_error(out, yy, mask=mask)
+
+    def _forward_masked(self, x, training, logits, return_mask=False):
         """``forward`` of a model with a step-mask producer (``_check_mask_flow``): layer by layer, the mask
         handed from its producer to the recurrent layers behind it.  None of ``forward``'s graph-level fusions
         is applied, in front of the mask producer or behind its consumer either: a ``Dense`` ->
         ``Activation('relu')`` head of a masked model runs as two launches (same numbers), and only the final
-        softmax is still skipped for the fused loss."""
+        softmax is still skipped for the fused loss.  ``return_mask`` (``_temporal_loss`` only) also returns the
+        mask still in flight at the output, or None; ``forward`` and ``predict`` return the outputs alone."""
         mask = None
         last = self.layers[-1]
         for l in self.layers:
@@ -662,7 +718,7 @@ class Sequential(Model):
                     mask = None
             else:
                 x = l.call(x, training)
-        return x
+        return (x, mask) if return_mask else x
 
     def _convbn_unit(self, conv, bn, x):
         """The (conv, BN) pair as a ``fused_blocks`` unit when the fused training node applies: no conv

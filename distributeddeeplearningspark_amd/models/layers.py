@@ -116,6 +116,74 @@ class Dense(Layer):
                 "use_bias": self.use_bias, "kernel_initializer": self.kernel_initializer}
 
 
+class TimeDistributed(Layer):
+    """Keras ``TimeDistributed(Dense(...))``: the wrapped ``Dense`` applied to every time step of ``[B, T, F]``:
+    one GEMM over the ``B * T`` rows (``ops.linear`` takes the rank-3 input as is), no kernels of its own.  It marks
+    the model's per-time-step head: a ``Sequential`` whose last layer with weights is a ``TimeDistributed`` takes the
+    temporal losses (``ops/loss.py``), masked by the step mask when one reaches it.
+
+    Weights (Keras order): kernel, bias; parameter names ``<wrapper>/<layer>/kernel`` and ``<wrapper>/<layer>/bias``."""
+
+    passes_mask = True
+    supports_skip = True
+
+    def __init__(self, layer, **kw):
+        if isinstance(layer, dict):  # a Keras config ({"class_name", "config"})
+            from .core import layer_from_config
+
+            layer = layer_from_config(layer)
+        if type(layer) is not Dense:
+            raise ValueError("TimeDistributed wraps a Dense layer")
+        if "input_shape" not in kw and "batch_input_shape" not in kw and layer._input_shape_arg is not None:
+            kw["input_shape"] = layer._input_shape_arg
+        super().__init__(**kw)
+        self.layer = layer
+        cfg = layer.get_config()
+        cfg.pop("batch_input_shape", None)
+        self.inner = Dense.from_config({**cfg, "name": f"{self.name}/{layer.name}"})
+        self.trainable = self._trainable  # now that the copy exists: hand it on
+
+    # the weights live in the inner Dense (it also owns the gradient hook the data-parallel engine installs on
+    # layers with parameters), so freezing the wrapper freezes that copy
+    @property
+    def trainable(self):
+        return self._trainable
+
+    @trainable.setter
+    def trainable(self, v):
+        self._trainable = bool(v)
+        inner = self.__dict__.get("inner")
+        if inner is not None:
+            inner.trainable = self._trainable and self.layer.trainable
+
+    @property
+    def activation_name(self):
+        return self.inner.activation_name
+
+    @property
+    def units(self):
+        return self.inner.units
+
+    def sublayers(self):
+        return [self.inner]
+
+    def build(self, s):
+        if len(s) < 2:
+            raise ValueError(f"TimeDistributed expects an input with a time axis ([T, F]), got {tuple(s)}")
+        self.inner.ensure_built(s)
+
+    def compute_output_shape(self, s):
+        return tuple(self.inner.compute_output_shape(s))
+
+    def call(self, x, training=False, skip_activation=False):
+        if x.dim() < 3:
+            raise ValueError(f"TimeDistributed expects [B, T, F] input, got {tuple(x.shape)}")
+        return self.inner.call(x, training, skip_activation=skip_activation)
+
+    def get_config(self):
+        return {**super().get_config(), "layer": {"class_name": "Dense", "config": self.layer.get_config()}}
+
+
 class Conv2D(Layer):
     def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", activation=None, use_bias=True,
                  dilation_rate=(1, 1), kernel_initializer="glorot_uniform", data_format=None, **kw):

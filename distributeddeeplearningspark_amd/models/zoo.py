@@ -7,6 +7,9 @@
 * ``bigru_regressor`` / ``bilstm_regressor``  the same regressors with a ``Bidirectional`` (concat) recurrent layer.
 * ``text_lstm_classifier``  Embedding(mask_zero) -> LSTM -> Dense(1, sigmoid) over zero-padded token ids
                       (``utils.pad_sequences``); ``masked_gru_regressor``  Masking -> GRU -> Dense over padded series.
+* ``sequence_tagger``  Embedding(mask_zero) -> Bidirectional(LSTM, sequences) -> TimeDistributed(Dense(tags, softmax));
+                      ``masked_seq2seq_regressor``  Masking -> GRU(sequences) -> TimeDistributed(Dense): one output per
+                      time step, the padded steps left out of the loss (``ops/loss.py`` temporal losses).
 * ``lenet5``          LeNet-5 on MNIST shape (BASELINE.json config #1).
 * ``vgg16``           VGG-16 (BN) in the CIFAR shape (BASELINE.json config #4).
 * ResNet-50 lives in ``resnet.py``; BERT-base in ``bert.py``.
@@ -15,7 +18,7 @@ from __future__ import annotations
 
 from .core import Sequential
 from .layers import (GRU, LSTM, Activation, BatchNormalization, Bidirectional, Conv2D, Dense, Dropout, Embedding,
-                     Flatten, Masking, MaxPooling2D)
+                     Flatten, Masking, MaxPooling2D, TimeDistributed)
 
 
 def mnist_cnn(nb_classes: int = 10, input_shape=(28, 28, 1), nb_filters: int = 32) -> Sequential:
@@ -80,6 +83,28 @@ def masked_gru_regressor(units: int = 128, seq_len: int = 25, features: int = 1,
     m.add(Masking(mask_value=mask_value, input_shape=(seq_len, features)))
     m.add(GRU(units, dropout=dropout, recurrent_dropout=recurrent_dropout))
     m.add(Dense(outputs, activation="linear"))
+    return m
+
+
+def sequence_tagger(vocab_size: int, maxlen: int, num_tags: int, embed_dim: int = 32, units: int = 64) -> Sequential:
+    """One tag per token of a zero-padded id sequence (id 0 is padding): the padded steps are skipped by the
+    BiLSTM and left out of the loss (``sparse_categorical_crossentropy`` with ``[B, maxlen]`` tag ids, or
+    ``categorical_crossentropy`` with one-hot ``[B, maxlen, num_tags]``)."""
+    m = Sequential()
+    m.add(Embedding(vocab_size, embed_dim, mask_zero=True, input_shape=(maxlen,)))
+    m.add(Bidirectional(LSTM(units, return_sequences=True)))
+    m.add(TimeDistributed(Dense(num_tags, activation="softmax")))
+    return m
+
+
+def masked_seq2seq_regressor(units: int = 128, seq_len: int = 25, features: int = 1, outputs: int = 1,
+                             mask_value: float = 0.0) -> Sequential:
+    """Many-to-many regression over ragged series padded with ``mask_value`` to ``seq_len`` steps: one output per
+    step, the padded steps left out of the loss (``mean_squared_error`` / ``mean_absolute_error``)."""
+    m = Sequential()
+    m.add(Masking(mask_value=mask_value, input_shape=(seq_len, features)))
+    m.add(GRU(units, return_sequences=True))
+    m.add(TimeDistributed(Dense(outputs, activation="linear")))
     return m
 
 

@@ -116,6 +116,150 @@ def mean_absolute_error(pred, target):
     return (pred.float() - target.float()).abs().mean()
 
 
+# ------------------------------------------------------------------------------------------------
+# Masked per-time-step losses of a [B, T, .] output (Keras 2 ``weighted_masked_objective``:
+# ``mean(score * mask / mean(mask))`` = ``sum(score * mask) / sum(mask)``).  ``mask`` is the uint8 [B, T]
+# step mask of ``ops/mask.py`` (None: every step counts).  The normaliser ``1 / max(sum(mask), 1)`` is counted on
+# the device, so a batch whose every step is masked gives a loss of exactly 0 and zero gradients (Keras divides
+# by zero there and returns NaN).  A masked step is selected out, not multiplied by 0: whatever stands at it
+# (NaN, a label outside the classes) never reaches the loss or the gradient, and its gradient row is zeros.
+def _temporal_fp32(what, *tensors):
+    for t in tensors:
+        if t is not None and t.is_floating_point() and t.dtype != torch.float32:
+            raise ValueError(f"{what} runs in fp32 (masked and recurrent models keep fp32), got {t.dtype}")
+
+
+def _flat_mask(mask, B, T):
+    if mask is None:
+        return None
+    if tuple(mask.shape) != (B, T):
+        raise ValueError(f"the step mask must be [{B}, {T}], got {tuple(mask.shape)}")
+    return mask.reshape(B * T)
+
+
+class _TemporalXentFn(torch.autograd.Function):
+    """Temporal softmax cross-entropy over rows [R, K]: count (masked only), sweep, row reduce: at most three
+    HIP launches; the sweep stores dlogits, the backward hands them out."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, probs, mask):
+        R, K = logits.shape
+        if use_native(logits):
+            lg = logits.contiguous()
+            dev = lg.device
+            dl = torch.empty_like(lg)
+            rows = torch.empty(R, dtype=torch.float32, device=dev)
+            loss = torch.empty(1, dtype=torch.float32, device=dev)
+            lab = None if labels is None else labels.to(torch.int64).contiguous()
+            pr = None if probs is None else probs.contiguous()
+            inv = None
+            if mask is not None:
+                mask = mask.to(torch.uint8).contiguous()
+                inv = torch.empty(1, dtype=torch.float32, device=dev)
+                C().mask_count_inv(mask, inv)
+            C().temporal_xent(lg, lab, pr, mask, inv, 1.0 / max(R, 1), rows, dl)
+            C().rows_sum_scaled(rows, 1.0 if inv is not None else 1.0 / max(R, 1), inv, loss)
+            ctx.save_for_backward(dl)
+            return loss.view(())
+        with torch.enable_grad():
+            lg = logits.detach().requires_grad_(True)
+            keep = torch.ones(R, dtype=torch.bool, device=lg.device) if mask is None else mask.bool()
+            cnt = keep.sum().clamp_min(1).to(torch.float32)
+            if labels is not None:
+                lab = labels.long()
+                keep = keep & (lab >= 0) & (lab < K)  # a label outside the classes: no loss, no gradient
+            rows_kept = lg[keep]  # selection: nothing at a dropped row enters the graph
+            lp = F.log_softmax(rows_kept, dim=-1)
+            if labels is not None:
+                ce = -lp.gather(1, lab[keep][:, None])[:, 0]
+            else:
+                ce = -(probs[keep] * lp).sum(-1)
+            out = ce.sum() / cnt
+            (dl,) = torch.autograd.grad(out, [lg])
+        ctx.save_for_backward(dl)
+        return out.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return (dl if unit_seed(ctx) else dl * g), None, None, None
+
+
+def temporal_softmax_cross_entropy(logits, labels=None, probs=None, mask=None):
+    """Per-step CE of ``softmax(logits [B, T, K])`` (softmax over K) against class ``labels [B, T]`` or target
+    ``probs [B, T, K]``, averaged over the steps where ``mask [B, T]`` is set: ``sum_r mask_r CE_r / max(sum(mask), 1)``.
+    A batch with every step masked gives exactly 0 (Keras gives NaN); see the section comment above."""
+    if (labels is None) == (probs is None):
+        raise ValueError("pass exactly one of labels / probs")
+    if logits.dim() != 3:
+        raise ValueError(f"temporal_softmax_cross_entropy expects [B, T, K] logits, got {tuple(logits.shape)}")
+    _temporal_fp32("temporal_softmax_cross_entropy", logits, probs)
+    B, T, K = logits.shape
+    if labels is not None:
+        if labels.numel() != B * T:
+            raise ValueError(f"labels must be [{B}, {T}], got {tuple(labels.shape)}")
+        labels = labels.reshape(B * T)
+    else:
+        if tuple(probs.shape) != (B, T, K):
+            raise ValueError(f"probs must be [{B}, {T}, {K}], got {tuple(probs.shape)}")
+        probs = probs.reshape(B * T, K)
+    return _TemporalXentFn.apply(logits.reshape(B * T, K), labels, probs, _flat_mask(mask, B, T))
+
+
+class _TemporalRegFn(torch.autograd.Function):
+    """Temporal MSE / MAE over rows [R, F]: ONE HIP launch counts the mask, computes the loss and stores the
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, mae):
+        R, Fd = pred.shape
+        if use_native(pred):
+            p = pred.contiguous()
+            loss = torch.empty((), dtype=torch.float32, device=p.device)
+            grad = torch.empty_like(p)
+            C().temporal_reg(p, target.contiguous(), None if mask is None else mask.to(torch.uint8).contiguous(),
+                             bool(mae), loss, grad)
+            ctx.save_for_backward(grad)
+            return loss
+        with torch.enable_grad():
+            pg = pred.detach().requires_grad_(True)
+            keep = torch.ones(R, dtype=torch.bool, device=pg.device) if mask is None else mask.bool()
+            cnt = keep.sum().clamp_min(1).to(torch.float32)
+            d = pg[keep] - target[keep]
+            score = (d.abs() if mae else d * d).mean(-1)
+            out = score.sum() / cnt
+            (grad,) = torch.autograd.grad(out, [pg])
+        ctx.save_for_backward(grad)
+        return out.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad if unit_seed(ctx) else grad * g), None, None, None
+
+
+def _temporal_reg(what, pred, target, mask, mae):
+    if pred.dim() != 3:
+        raise ValueError(f"{what} expects [B, T, F] predictions, got {tuple(pred.shape)}")
+    if target.numel() != pred.numel():
+        raise ValueError(f"{what}: target {tuple(target.shape)} does not match pred {tuple(pred.shape)}")
+    _temporal_fp32(what, pred, target)
+    B, T, Fd = pred.shape
+    return _TemporalRegFn.apply(pred.reshape(B * T, Fd), target.reshape(B * T, Fd), _flat_mask(mask, B, T), mae)
+
+
+def temporal_mean_squared_error(pred, target, mask=None):
+    """``sum_r mask_r mean_F (pred - target)^2 / max(sum(mask), 1)`` of ``[B, T, F]`` inputs and a ``[B, T]`` step
+    mask (exactly 0 when every step is masked, where Keras gives NaN)."""
+    return _temporal_reg("temporal_mean_squared_error", pred, target, mask, False)
+
+
+def temporal_mean_absolute_error(pred, target, mask=None):
+    """``sum_r mask_r mean_F |pred - target| / max(sum(mask), 1)``; the gradient is ``sign(pred - target)`` with
+    ``sign(0) = 0`` (exactly 0 when every step is masked, where Keras gives NaN)."""
+    return _temporal_reg("temporal_mean_absolute_error", pred, target, mask, True)
+
+
 def binary_crossentropy(pred, target, eps=1e-7):
     p = pred.float().clamp(eps, 1 - eps)
     t = target.float()
